@@ -8,12 +8,18 @@ Workloads (all BASELINE.json shapes: 2 states, length 30, 2-D, nb_substeps=1, fr
   c2   configs[1], 1e6 tracks PER GPU (weak scaling)              - the headline on ONE GPU
   c2s  configs[1], 1e6 tracks IN TOTAL, row-sharded (strong)      - the headline on N > 1 GPUs (what BASELINE.json's metric names)
   c4   configs[3], 1e7 tracks in total, row-sharded (strong)
-Without ``--config``, an N > 1 run measures all three back to back (`scaling_runs`), each with ms_per_step, kernel_ms and
-comm_ms = step - kernel; with ``--config`` only that one.  At N = 1 an `extra` block (outside the timed region) reports the other
-BASELINE configs on the same GPU: configs[2] (3 states, 46 length buckets), configs[4] (4 states, nb_substeps 3) and its predict_Bs
-annotation, configs[3] on one GPU, each with algorithmic bytes and the flop model of SURVEY.md section 8(d).
+A plain run measures the headline workload only: set-up, warm-up, the timed steps, the result line.  Everything else is measured
+with ``--full`` (after the timed region): without ``--config``, an N > 1 run then measures all three workloads back to back
+(`scaling_runs`), each with ms_per_step, kernel_ms and comm_ms = step - kernel.  At N = 1 it adds the exact gradient and the
+threshold-fusion kernels on the headline data, the CPU baselines, and an `extra` block that reports the other BASELINE configs on
+the same GPU: configs[2] (3 states, 46 length buckets), configs[4] (4 states, nb_substeps 3) and its predict_Bs annotation,
+configs[3] on one GPU, each with algorithmic bytes and the flop model of SURVEY.md section 8(d).
+
+``--dump-outputs DIR`` writes what the timed step returned in its last step, the log-likelihood sum of the whole dataset, as
+DIR/loglik.npy (float64, shape [1]).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python bench.py --gpus N ...            # starts its own N rank processes (one per GPU) and relays rank 0's JSON line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
@@ -549,11 +555,17 @@ def main(argv=None):
     ap.add_argument("--config", choices=("c2", "c2s", "c4"), default=None,
                     help="c2: BASELINE configs[1], 1e6 tracks PER GPU (weak scaling); c2s: the same 1e6 tracks IN TOTAL, row-sharded (strong "
                          "scaling - what BASELINE.json's metric names); c4: configs[3], 1e7 tracks in total, row-sharded (strong).  Default: "
-                         "c2 on one GPU; on N > 1 GPUs c2s is the headline and c2 (weak) + c4 (strong) are measured in the same run (`scaling_runs`)")
+                         "c2 on one GPU; on N > 1 GPUs c2s is the headline, and with --full c2 (weak) + c4 (strong) are measured in the same run "
+                         "(`scaling_runs`)")
     ap.add_argument("--tracks", type=int, default=None, help="tracks per GPU (c2) / in total (c2s, c4); default = the BASELINE config")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[2] / configs[4] measurements after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fits", action="store_true", help="extra block: single evaluations of every kernel only, no whole param_fitting runs (profiler passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else: the other workloads at N > 1; at N = 1 the gradient and threshold-fusion "
+                         "kernels, the `extra` block and the CPU baselines (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the log-likelihood sum the last timed step returned as DIR/loglik.npy (float64)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the configs[2] / configs[4] measurements after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-fits", action="store_true", help="--full, extra block: single evaluations of every kernel only, no whole param_fitting runs (profiler passes)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend: nccl = RCCL over xGMI (the measurement); gloo = rehearsal of the multi-rank control flow on a box "
                          "without GPUs (needs --rehearsal-context; nothing it prints is a measurement)")
@@ -561,6 +573,8 @@ def main(argv=None):
                     help="gloo rehearsal only (tests/test_bench_gloo.py): class under tests/ that stands in for the device context")
     argv = list(sys.argv[1:] if argv is None else argv)
     a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.backend == "nccl" and a.rehearsal_context:
         raise SystemExit("--rehearsal-context is only valid with --backend gloo: the measurement always runs the HIP library")
     if a.backend == "gloo" and not a.rehearsal_context:
@@ -659,13 +673,16 @@ def main(argv=None):
         ts.close()
         return res, None, None
 
-    # the headline workload (resident in HBM before the timed region); N > 1 without --config: all three scaling workloads in this run
+    # the headline workload (resident in HBM before the timed region); --full at N > 1 without --config: all three scaling workloads in this run
     primary = a.config if a.config else ("c2" if world == 1 else "c2s")
     scaling_runs = {}
-    if a.config is None and world > 1:
+    if a.full and a.config is None and world > 1:
         for cfg in ("c2", "c4"):
             scaling_runs[cfg] = run_config(cfg, None)[0]
     head, ts, model = run_config(primary, a.tracks, keep=True)
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "loglik.npy"), np.array([-head["neg_loglik"]], dtype=np.float64))
     scaling_runs[primary] = dict(head)
     a.tracks, total_tracks, scaling = head["tracks_per_gpu"], head["total_tracks"], head["scaling"]
     dt_all = head["ms_per_step"] * 1e-3 * a.steps
@@ -678,7 +695,8 @@ def main(argv=None):
     launch_info = ts.ctx.last_launch_info()
     th = None
     grad_info = None
-    if on_gpu and world == 1 and a.tracks == N_TRACKS and a.config == "c2":
+    full_c2 = a.full and on_gpu and world == 1 and a.tracks == N_TRACKS and a.config == "c2"
+    if full_c2:
         from extrack_amd import gradient
         pg = tracking.generate_params(nb_states=2, LocErr_type=1, estimated_Ds=[1e-3, DS_COEF[1]], estimated_LocErr=[LOCERR], estimated_Fs=[FS[0]],
                                       estimated_transition_rates=0.1)
@@ -688,7 +706,7 @@ def main(argv=None):
         grad_info = {"what": "BASELINE configs[1] data: -sum(LL) AND its exact gradient (7 free parameters) in one pass of the gradient kernel "
                              "(extrack_loglik_grad), the evaluation an analytic-gradient BFGS iteration costs",
                      "kernel_ms": ts.ctx.last_grad_ms(), "n_directions": len(gnames), "grad_inf_norm": float(np.abs(gg).max())}
-    if on_gpu and world == 1 and a.tracks == N_TRACKS and a.config == "c2":
+    if full_c2:
         for _ in range(2):
             th_val = ts.loglik_th(model, 0.2, 120, 2000)
         torch.cuda.synchronize()
@@ -717,7 +735,7 @@ def main(argv=None):
               "launch": ts.ctx.last_launch_info()}
     ts.close()
     extra = None
-    if on_gpu and world == 1 and a.config == "c2" and a.tracks == N_TRACKS and not a.no_extra:
+    if full_c2 and not a.no_extra:
         extra = other_configs(local, a.no_cpu_baseline, a.no_fits)
         # configs[3] on ONE GPU: the N = 1 point of the strong-scaling curve `scaling_runs.c4` reports at N > 1
         scaling_runs["c4"] = run_config("c4", None)[0]
@@ -791,7 +809,7 @@ def main(argv=None):
         out["loglik_gradient"] = grad_info
     if extra is not None:
         out["extra"] = extra
-    if not a.no_cpu_baseline and world == 1 and on_gpu:
+    if a.full and not a.no_cpu_baseline and world == 1 and on_gpu:
         out["cpu_baseline"] = cpu_baseline()
         out["speedup_vs_cpu_baseline"] = evals_per_s / out["cpu_baseline"]["value"]
         try:

@@ -54,11 +54,11 @@ def test_bench_self_launch_weak_and_strong():
 
 
 def test_bench_default_multi_gpu_run_reports_all_three_workloads():
-    """No --config at N > 1: c2s (strong, 1e6 tracks in total at full size) is the headline, c2 (weak) and c4 (strong) ride along.
-    EXTRACK_BENCH_N_TRACKS scales the "1e6" of all three down to what the oracle-backed stand-in evaluates in seconds."""
+    """--full without --config at N > 1: c2s (strong, 1e6 tracks in total at full size) is the headline, c2 (weak) and c4 (strong) ride
+    along.  EXTRACK_BENCH_N_TRACKS scales the "1e6" of all three down to what the oracle-backed stand-in evaluates in seconds."""
     os.environ["EXTRACK_BENCH_N_TRACKS"] = "60"
     try:
-        r = _bench("--gpus", "2", "--steps", "1", "--warmup", "1")
+        r = _bench("--gpus", "2", "--steps", "1", "--warmup", "1", "--full")
     finally:
         os.environ.pop("EXTRACK_BENCH_N_TRACKS")
     assert r.returncode == 0, r.stderr[-2000:]
@@ -70,6 +70,25 @@ def test_bench_default_multi_gpu_run_reports_all_three_workloads():
     assert runs["c2s"]["total_tracks"] == 60 and runs["c2s"]["tracks_per_gpu"] == 30
     for k in ("c2", "c2s", "c4"):
         assert runs[k]["ms_per_step"] > 0 and "comm_ms" in runs[k] and np.isfinite(runs[k]["neg_loglik"])
+
+
+def test_bench_plain_run_measures_the_headline_only_and_dumps_its_output(tmp_path):
+    """Without --full only the headline workload runs; --dump-outputs writes the value its last timed step returned (the all-reduced
+    log-likelihood sum), and the seeded inputs make a second run write the same array."""
+    os.environ["EXTRACK_BENCH_N_TRACKS"] = "60"
+    try:
+        runs = [_bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / k)) for k in ("a", "b")]
+    finally:
+        os.environ.pop("EXTRACK_BENCH_N_TRACKS")
+    for r in runs:
+        assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(runs[0].stdout.strip().split("\n")[-1])
+    assert d["config"]["name"] == "c2s" and d["steps"] == 3 and d["ms_per_step"] > 0
+    assert set(d["scaling_runs"]) - {"note"} == {"c2s"}
+    assert "extra" not in d and "cpu_baseline" not in d
+    ll = np.load(tmp_path / "a" / "loglik.npy")
+    assert ll.dtype == np.float64 and ll.shape == (1,) and ll[0] == -d["neg_loglik"]
+    assert np.array_equal(ll, np.load(tmp_path / "b" / "loglik.npy"))
 
 
 def test_bench_propagates_a_failing_rank():

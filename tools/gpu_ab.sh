@@ -3,6 +3,6 @@
 cd $GRAFT_REPO_ROOT
 for round in 1 2 3; do
   for lib in "$@"; do
-    EXTRACK_HIP_LIB=$PWD/$lib python bench.py --no-cpu-baseline --no-extra --steps 30 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$lib', round(d['roofline']['kernel_ms'],4), round(d['ms_per_step'],4), round(d['threshold_fusion']['kernels_ms'],4))"
+    EXTRACK_HIP_LIB=$PWD/$lib python bench.py --full --no-cpu-baseline --no-extra --steps 30 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$lib', round(d['roofline']['kernel_ms'],4), round(d['ms_per_step'],4), round(d['threshold_fusion']['kernels_ms'],4))"
   done
 done
