@@ -104,6 +104,20 @@ XT_HD void xt_exp_tab_x2(double x0, double x1, double& p0, double& p1, int& j0, 
     xt_f2_exp_bits(t0, j0, e0);
     xt_f2_exp_bits(t1, j1, e1);
 }
+// One evaluation of the same (the warm-up chain of xt_reg2.h: one sequence per lane).
+XT_HD void xt_exp_tab_x1(double x, double& p, int& j, int& e)
+{
+    x = x > XT_F2_XCLAMP ? x : XT_F2_XCLAMP;
+    const double t = xt_fma(x, XT_F2_EXP_SCALE, XT_MAGIC);
+    const double k = t - XT_MAGIC;
+    double r = xt_fma(k, XT_F2_EXP_HI, x);
+    r = xt_fma(k, XT_F2_EXP_LO, r);
+    double q = 1.66666666666666666667e-01;
+    q = xt_fma(q, r, XT_F2_EXP_C2);
+    q = xt_fma(q, r, 1.0);
+    p = xt_fma(q, r, 1.0);
+    xt_f2_exp_bits(t, j, e);
+}
 // TB[i] = 2^(i / 1024) = T64[i >> 4] * exp((i & 15) ln2 / 1024) at byte offset `off` of the workgroup's LDS; T64: the blob's table (already
 // staged).  The second factor: Taylor to s^7 (s <= 0.0102: truncation far below 1e-18).  Call between two workgroup barriers.
 template <class Ctx>

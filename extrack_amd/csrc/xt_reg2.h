@@ -70,9 +70,13 @@ struct XtR2Lane {
 // immediate).  tab: byte address of the transition table in use (T or T * stay).  A variant with a run-time phase - one step body, the
 // exchange picked by a switch - was measured 1.8x SLOWER with 7 directions (16.4 -> 43.8 ms on C2: the switches cut the step into
 // basic blocks the scheduler cannot overlap).
-template <int F, int D, int K, int NP, int H, bool ZF, bool LAZY, int VAR, class Ctx>
+// FIRST: step F - 1 right after the warm-up chain (xt_r2_chain; likelihood only, zero-free): member 1 is dead and member 0 holds a
+// normalised mantissa, so there is nothing to merge - the step runs on member 0 at unit weight scale (W = 1, M = m0, U = u0; Wm, We = z0, e0)
+// and its shared reciprocal covers Dq[0] Dq[1] only.
+template <int F, int D, int K, int NP, int H, bool ZF, bool LAZY, int VAR, bool FIRST = false, class Ctx>
 XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const double* c, const double* l2)
 {
+    static_assert(!FIRST || (NP == 0 && ZF && LAZY), "the merge-free first step is a step of the zero-free likelihood-only loop");
     constexpr int NGB = F - 1;
     constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
     const int lane = xt_opaque(cx.lane());  // keeps the per-phase constants (prev, qa, table offsets) out of the loop-invariant registers
@@ -89,18 +93,18 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
     // ---- primal: merge, expand, integrate (xt_f2_step with the members in registers)
     const int e0 = s.e[0], e1 = s.e[1];
     const int emax = e0 > e1 ? e0 : e1;
-    const double w0 = xt_ldexp(s.z[0], e0 - emax), w1 = xt_ldexp(s.z[1], e1 - emax);
-    const double W = w0 + w1;
+    const double w0 = FIRST ? 1.0 : xt_ldexp(s.z[0], e0 - emax), w1 = FIRST ? 0.0 : xt_ldexp(s.z[1], e1 - emax);
+    const double W = FIRST ? 1.0 : w0 + w1;
     double M[D], U[K];
     XT_UNROLL
-    for (int d = 0; d < D; ++d) M[d] = xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
+    for (int d = 0; d < D; ++d) M[d] = FIRST ? s.m[0][d] : xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
     XT_UNROLL
-    for (int k = 0; k < K; ++k) U[k] = xt_fma(w1, s.u[1][k], w0 * s.u[0][k]);
+    for (int k = 0; k < K; ++k) U[k] = FIRST ? s.u[0][k] : xt_fma(w1, s.u[1][k], w0 * s.u[0][k]);
     const bool live = ZF ? true : W > 0.0;
     const double Ws = ZF ? W : (live ? W : 1.0);
     constexpr bool RN = !LAZY || (H % XT_F2_RENORM) == 0;
-    const double Wm = RN ? xt_frexp_mant(W) : W;
-    const int We = live ? (RN ? emax + xt_frexp_exp(W) : emax) : XT_EMIN;
+    const double Wm = FIRST ? s.z[0] : (RN ? xt_frexp_mant(W) : W);
+    const int We = FIRST ? e0 : (live ? (RN ? emax + xt_frexp_exp(W) : emax) : XT_EMIN);
 
     double Dq[2][K];
     XT_UNROLL
@@ -112,7 +116,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
         const double d01 = Dq[0][0] * Dq[1][0];
         const double R = xt_rcp(Ws * d01);
         const double RW = R * Ws;
-        rW = R * d01;
+        rW = FIRST ? 1.0 : R * d01;
         rD[0][0] = RW * Dq[1][0];
         rD[1][0] = RW * Dq[0][0];
     } else {
@@ -129,7 +133,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
         XT_UNROLL
         for (int i = 2 * K; i >= 0; --i) suf[i] = suf[i + 1] * f[i];
         const double R = xt_rcp(pre[2 * K + 1]);
-        rW = R * suf[1];
+        rW = FIRST ? 1.0 : R * suf[1];
         XT_UNROLL
         for (int q = 0; q < 2; ++q)
             XT_UNROLL
@@ -313,6 +317,72 @@ XT_HD int xt_r2_gmax(Ctx& cx, int v)
     return v;
 }
 
+// Warm-up of the likelihood-only recursion of a well-scaled launch: positions 1 .. T (T = min(L - 2, F - 2)), before the window is full.
+// No fusion happens there, so member 0 of a lane is ONE Kalman chain over positions 0 .. T along the state path of the lane's own group
+// bits (time 0 in GB[F-2], time t in GB[t-1]) and member 1 (a dummy oldest digit) stays dead.  Every lane computes on its own - one child
+// per position, no merge, no exchange, no zero-weight handling - what the merge / expand / exchange steps would leave in its registers;
+// shared prefixes are recomputed by the lanes that share them (in the stepped form those lanes idle).  Hands over a normalised mantissa
+// (the first full step, xt_r2_step<..., FIRST>, forms W^3-sized products).  A bucket too short to fill the window (T < F - 2) still has
+// dummy digits in GB[T .. F-3] at the last position: lanes with one of them set end at zero weight, as the stepped form leaves them.
+template <int F, int D, int K, int NP, class Ctx, class GetPos>
+XT_HD void xt_r2_chain(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int T, int stay_from, GetPos& getpos)
+{
+    constexpr int NGB = F - 1;
+    const int lane = xt_opaque(cx.lane());  // as in xt_r2_step: lane-derived constants stay out of the registers live across the step loop
+    double z = s.z[0];
+    int e = s.e[0];
+    XT_UNROLL
+    for (int t = 1; t < NGB; ++t) {
+        if (t > T) break;  // wave-uniform (per bucket)
+        const int prev = (lane >> xt_r2_gbit(F, t == 1 ? NGB - 1 : t - 2)) & 1;
+        const int q = (lane >> xt_r2_gbit(F, t - 1)) & 1;
+        const int io = (prev * 2 + q) * 8;  // [prev][q] byte offset
+        const double TT = xt_at<double>(lds, XT_R2_TAB0 + (t >= stay_from ? 32 : 0) + io);
+        const double d2 = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + io);
+        double c[D], l2[K];
+        getpos(t, c, l2);
+        double tt[K], r[K], dm[D], x = 0.0, gf;
+        XT_UNROLL
+        for (int k = 0; k < K; ++k) {
+            const double a = d2 + s.u[0][k];
+            r[k] = xt_rcp(l2[k] + a);
+            tt[k] = a * r[k];
+        }
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) dm[d] = c[d] - s.m[0][d];
+        if (K == 1) {
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) x = xt_fma(dm[d], dm[d], x);
+            x *= -0.5 * r[0];
+            gf = xt_pow_half<D>(r[0]);
+        } else {
+            double gg = 1.0;
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) {
+                x = xt_fma(-0.5 * dm[d] * dm[d], r[d], x);
+                gg *= r[d];
+            }
+            gf = sqrt(gg);
+        }
+        double p;
+        int j, n;
+        xt_exp_tab_x1(x, p, j, n);
+        z = (z * TT) * (gf * xt_at<double>(lds, XT_F2_EXPB_OFF + j * 8)) * p;
+        e += n;
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) s.m[0][d] = xt_fma(dm[d], tt[K == 1 ? 0 : d], s.m[0][d]);
+        XT_UNROLL
+        for (int k = 0; k < K; ++k) s.u[0][k] = l2[k] * tt[k];
+    }
+    int dummy = 0;  // lane bits of digits that are still dummies (time < 0)
+    XT_UNROLL
+    for (int i = 0; i < NGB - 1; ++i)
+        if (i >= T) dummy |= 1 << xt_r2_gbit(F, i);
+    const bool live = (lane & dummy) == 0;
+    s.z[0] = live ? xt_frexp_mant(z) : 0.0;
+    s.e[0] = live ? e + xt_frexp_exp(z) : XT_EMIN;
+}
+
 // NP == 0: log-likelihood only, per-block sums to a.partials (ga unused).  NP > 0: ga.gpartials[block][1 + NP] = {sum LL, sum dLL/dtheta_p}.
 template <int F, int D, int K, int NP, int VAR = 0, class Ctx>
 XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
@@ -354,6 +424,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     XT_UNROLL
     for (int k = 0; k < K; ++k) l2g[k] = hdr[k];
     const bool well_scaled = a.well_scaled != 0;
+    const bool chain = NP == 0 && well_scaled;  // warm-up as per-lane chains (xt_r2_chain)
 
     double* pos = (double*)(lds + xt_r2_pos0(NPT)) + wib * TPW * XT_F2_CHUNK * (D + KS);  // [TPW][CHUNK][D]
     double* sig = pos + TPW * XT_F2_CHUNK * D;                                           // [TPW][CHUNK][KS]
@@ -441,16 +512,12 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 #define XT_R2_TABSEL tab
         auto run_steps = [&](int& t, int tend, int tab) XT_INL {
             int ph = (t - 1) % NGB;
+            const int tend2 = tend;
             if (!well_scaled) {
-                const int tend2 = tend;
                 while (t <= tend2) { XT_R2_PHASES(false, false) }
                 return;
             }
-            {   // steps t < F merge a dummy digit (zero-weight member)
-                const int tend2 = tend < F - 1 ? tend : F - 1;
-                while (t <= tend2) { XT_R2_PHASES(false, true) }
-            }
-            const int tend2 = tend;
+            // well-scaled: positions 1 .. F - 1 are done by the warm-up chain and the merge-free first step (every lane live from here on)
             while (t <= tend2) { XT_R2_PHASES(true, true) }
         };
 #undef XT_R2_TABSEL
@@ -485,7 +552,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 constexpr int NBIT = xt_r2_gbit(F, NGB - 1);
                 double c0[D], l20[K];
                 getpos(0, c0, l20);
-                const bool live0 = (lane & (GMASK & ~(1 << NBIT))) == 0;
+                const bool live0 = chain || (lane & (GMASK & ~(1 << NBIT))) == 0;  // the chain masks the dummy digits at its end
                 const int s0 = (lane >> NBIT) & 1;
                 s.z[0] = live0 ? hdr[8 + s0] : 0.0;
                 s.e[0] = live0 ? 0 : XT_EMIN;
@@ -509,6 +576,21 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         for (int d = 0; d < D; ++d) s.dm[pp][q][d] = 0.0;
                         XT_UNROLL
                         for (int k = 0; k < K; ++k) s.du[pp][q][k] = xt_at<double>(lds, tb + k * 8);
+                    }
+                }
+                if constexpr (NP == 0) {
+                    if (chain) {
+                        // positions 1 .. F - 2 as per-lane chains, position F - 1 without the merge of the dead member: t = F after that
+                        const int T = L - 2 < NGB - 1 ? L - 2 : NGB - 1;
+                        xt_r2_chain<F>(cx, lds, s, T, stay_from, getpos);
+                        if (L - 2 >= F - 1) {
+                            double c[D], l2[K];
+                            getpos(F - 1, c, l2);
+                            xt_r2_step<F, D, K, NP, NGB - 1, true, true, VAR, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, l2);
+                            t = F;
+                        } else {
+                            t = L - 1 > 1 ? L - 1 : 1;
+                        }
                     }
                 }
             }

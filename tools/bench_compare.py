@@ -26,7 +26,7 @@ for k in sorted(set(a) & set(b)):
     if a[k] <= 0 or "cpu_baseline" in k or "speedup" in k:
         continue
     r = b[k] / a[k]
-    higher_better = any(s in k for s in ("per_s", "value"))
+    higher_better = k.rsplit(".", 1)[-1].endswith(("per_s", "value"))  # not "ms_per_step"
     worse = (r < 1 - tol) if higher_better else (r > 1 + tol)
     better = (r > 1 + tol) if higher_better else (r < 1 - tol)
     if worse or better:

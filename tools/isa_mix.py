@@ -5,8 +5,10 @@ reads the result (profiles/isa_mix.json) for its fp64-issue figures instead of h
     python tools/isa_mix.py            # compiles xt_ll_r2_kernel<6,2,1> into /tmp, writes profiles/isa_mix.json
 
 Method: the likelihood-only register-resident kernel (csrc/xt_reg2.h) unrolls its step loop over the F - 1 exchange phases in three
-variants; the basic blocks with >= 50 fp64 vector instructions and the table reads are the steps, and the 2 (F - 1) of them with the fewest
-instructions are the steady-state ones (well-scaled model: zero-free, lazily re-normalised).  Counts are per wave-step (one wavefront = 64 / 2^(F-1) tracks,
+variants; the basic blocks with >= 50 fp64 vector instructions and the table reads are the steps.  The steady-state ones (well-scaled model:
+zero-free, lazily re-normalised) are the 2 (F - 1) with the fewest instructions among the blocks of the innermost loops (the loop depth the
+compiler notes at every block label); the step outside them is the merge-free first step (position F - 1), and the F - 2 blocks with one
+v_rcp_f64 right before it are the warm-up chain (positions 1 .. F - 2, one block each).  Counts are per wave-step (one wavefront = 64 / 2^(F-1) tracks,
 one position)."""
 import json, os, re, subprocess, sys, tempfile
 
@@ -32,8 +34,12 @@ asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")][0]
 blocks, cur = [], None
 for line in open(os.path.join(tmp, asm)):
     if line.startswith(".LBB") or line.startswith("_Z"):
-        cur = dict(name=line.split(":")[0], f64=0, fma=0, valu32=0, lds=0, salu=0, vmem=0, trans=0)
+        dm = re.search(r"Depth=(\d+)", line)
+        cur = dict(name=line.split(":")[0], depth=int(dm.group(1)) if dm else 0, f64=0, fma=0, valu32=0, lds=0, salu=0, vmem=0, trans=0)
         blocks.append(cur)
+        continue
+    if cur is not None and line.lstrip().startswith(";") and "Depth=" in line:  # the loop comment may follow the label on a line of its own
+        cur["depth"] = int(re.search(r"Depth=(\d+)", line).group(1))
         continue
     if cur is None or not line.startswith("\t") or line.startswith("\t.") or line.startswith("\t;"):
         continue
@@ -54,7 +60,11 @@ for line in open(os.path.join(tmp, asm)):
     elif op.startswith(("global_", "flat_", "buffer_", "scratch_")):
         cur["vmem"] += 1
 steps = sorted([b for b in blocks if b["f64"] >= 50 and b["lds"] >= 4], key=lambda b: b["f64"] + b["valu32"])
-ss = steps[:2 * (F - 1)]  # the step loop is inlined twice (before / after the stay-in-FOV factor sets in): both copies of the F - 1 phases
+maxd = max(b["depth"] for b in steps)
+ss = [b for b in steps if b["depth"] == maxd][:2 * (F - 1)]  # the step loop is inlined twice (before / after the stay-in-FOV factor sets in): both copies of the F - 1 phases
+first = [b for b in steps if b["depth"] < maxd]
+at = blocks.index(first[0]) if len(first) == 1 else 0
+chain = [b for b in blocks[:at] if b["depth"] == maxd - 1 and 20 <= b["f64"] < 50 and b["trans"] == 1][-(F - 2):] if at else []
 n = float(len(ss))
 mix = {k: sum(b[k] for b in ss) / n for k in ("f64", "fma", "valu32", "lds", "salu", "vmem", "trans")}
 tpw = 64 >> (F - 1)
@@ -66,7 +76,16 @@ out = {"kernel": "xt_ll_r2_kernel<%d,%d,%d> (steady-state step, mean over the %d
        "method": "tools/isa_mix.py: hipcc --save-temps of the current csrc/xt_reg2.h; an fp64 vector instruction issues in 4 cycles per wavefront, "
                  "a 32-bit one (incl. the DPP moves of the lane exchange) in 2 (profiles/r01_valu_rates.txt); a v_permlane swap is counted as 32-bit",
        "step_blocks": [(b["name"], b["f64"], b["valu32"], b["lds"]) for b in steps]}
+# per-track fixed cost of the warm-up (once per wave-batch): the chain blocks together, the first full step
+out["warmup_chain_blocks"] = [(b["name"], b["f64"], b["valu32"], b["lds"]) for b in chain]
+out["warmup_chain_fp64"] = sum(b["f64"] for b in chain)
+out["warmup_chain_valu32"] = sum(b["valu32"] for b in chain)
+out["warmup_chain_issue_cycles"] = 4 * out["warmup_chain_fp64"] + 2 * out["warmup_chain_valu32"]
+out["first_step_blocks"] = [(b["name"], b["f64"], b["valu32"], b["lds"]) for b in first]
+out["first_step_fp64"] = sum(b["f64"] for b in first)
+out["first_step_valu32"] = sum(b["valu32"] for b in first)
+out["first_step_issue_cycles"] = 4 * out["first_step_fp64"] + 2 * out["first_step_valu32"]
 path = os.path.join(ROOT, "profiles", "isa_mix.json")
 json.dump(out, open(path, "w"), indent=1)
-print(json.dumps({k: v for k, v in out.items() if k != "step_blocks"}, indent=1))
+print(json.dumps({k: v for k, v in out.items() if not k.endswith("_blocks")}, indent=1))
 print("step blocks (name, fp64, 32-bit valu, lds):", out["step_blocks"])
