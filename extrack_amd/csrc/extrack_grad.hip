@@ -258,7 +258,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             for (auto& d : descs) Lmax0 = std::max(Lmax0, (int)d.L);
             const size_t slot_doubles = (size_t)tpb * std::max(Lmax0 - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
             const size_t max_blocks = (ctx->rev_log_mb << 20) / (slot_doubles * sizeof(double));
-            const bool use_rev = kp && lds <= 160 * 1024 && max_blocks >= (size_t)ctx->n_cu / 2 &&
+            const bool use_rev = kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
                                  (ctx->grad_rev == 2 || (ctx->grad_rev == 1 && ctx->grad_reg2 == 1 && !r2));
             if (use_rev) {
                 if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -276,22 +276,12 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                 XtRevArgs ra;
                 memset(&ra, 0, sizeof(ra));
                 const double target = std::min((double)occ * ctx->n_cu * ctx->rev_oversub, (double)max_blocks);
-                double wsum = 0.0;
                 int Lmax = 2;
-                std::vector<int64_t> nbatch(descs.size());
-                for (size_t i = 0; i < descs.size(); ++i) {
-                    nbatch[i] = (descs[i].N + tpb - 1) / tpb;
-                    wsum += (double)nbatch[i] * (descs[i].L - 1);
-                    Lmax = std::max(Lmax, (int)descs[i].L);
-                }
-                int64_t acc = 0;
-                for (size_t i = 0; i < descs.size(); ++i) {
-                    int64_t n = (int64_t)ceil(target * ((double)nbatch[i] * (descs[i].L - 1)) / wsum);
-                    n = n < 1 ? 1 : (n > nbatch[i] ? nbatch[i] : n);
-                    acc += n;
-                    a.blk_end[i] = (int32_t)acc;
-                }
-                const int grid = (int)acc;
+                for (size_t i = 0; i < descs.size(); ++i) Lmax = std::max(Lmax, (int)descs[i].L);
+                // at most max_blocks log regions: the budget holds for the launched grid, not only for the target
+                const int64_t sg = xt_split_descs(target, (int64_t)std::min<size_t>(max_blocks, INT64_MAX), descs, tpb, a.blk_end);
+                if (sg < 0) return xt_fail(ctx, EXTRACK_E_INVALID, "reverse-mode gradient: no grid split within the log budget");
+                const int grid = (int)sg;
                 ra.TB = TB;
                 ra.log_stride = (int64_t)std::max(Lmax - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
                 if ((rc = xt_grad_reserve(ctx, &ctx->d_revlog, &ctx->revlog_cap, (size_t)grid * tpb * (size_t)ra.log_stride))) return rc;
@@ -373,20 +363,10 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                 }
                 const int occ = it->second;
                 const double target = (double)occ * ctx->n_cu * ctx->oversub;
-                double wsum = 0.0;
-                std::vector<int64_t> nbatch(descs.size());
-                for (size_t i = 0; i < descs.size(); ++i) {
-                    nbatch[i] = (descs[i].N + tpb - 1) / tpb;
-                    wsum += (double)nbatch[i] * (descs[i].L - 1);
-                }
-                int64_t acc = 0;
-                for (size_t i = 0; i < descs.size(); ++i) {
-                    int64_t n = (int64_t)ceil(target * ((double)nbatch[i] * (descs[i].L - 1)) / wsum);
-                    n = n < 1 ? 1 : (n > nbatch[i] ? nbatch[i] : n);
-                    acc += n;
-                    a.blk_end[i] = (int32_t)acc;
-                }
-                const int grid = (int)acc;
+                // at most as many blocks as the free part of the partial-sum buffer has rows
+                const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NPT + 1)), descs, tpb, a.blk_end);
+                if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
+                const int grid = (int)sg;
                 if (poff + (size_t)grid * (NPT + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
                 a.desc = ctx->d_desc + doff;
                 a.ndesc = (int32_t)descs.size();
@@ -453,20 +433,10 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                     XtGradArgs ga;
                     memset(&ga, 0, sizeof(ga));
                     const double target = (double)occ * ctx->n_cu * 4;
-                    double wsum = 0.0;
-                    std::vector<int64_t> nbatch(descs.size());
-                    for (size_t i = 0; i < descs.size(); ++i) {
-                        nbatch[i] = (descs[i].N + tpb - 1) / tpb;
-                        wsum += (double)nbatch[i] * (descs[i].L - 1);
-                    }
-                    int64_t acc = 0;
-                    for (size_t i = 0; i < descs.size(); ++i) {
-                        int64_t n = (int64_t)ceil(target * ((double)nbatch[i] * (descs[i].L - 1)) / wsum);
-                        n = n < 1 ? 1 : (n > nbatch[i] ? nbatch[i] : n);
-                        acc += n;
-                        a.blk_end[i] = (int32_t)acc;
-                    }
-                    const int grid = (int)acc;
+                    // at most as many blocks as the free part of the partial-sum buffer has rows
+                    const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NP + 1)), descs, tpb, a.blk_end);
+                    if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
+                    const int grid = (int)sg;
                     if (poff + (size_t)grid * (NP + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
                     a.desc = ctx->d_desc + doff;
                     a.ndesc = (int32_t)descs.size();
@@ -531,20 +501,10 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             // grid: blocks per bucket in proportion to its work, CUs oversubscribed (as the likelihood launcher does)
             const int occ = std::max(1, std::min((int)((160 * 1024) / l.lds), 2048 / threads));
             const double target = (double)occ * ctx->n_cu * 4;
-            double wsum = 0.0;
-            std::vector<int64_t> nbatch(descs.size());
-            for (size_t i = 0; i < descs.size(); ++i) {
-                nbatch[i] = (descs[i].N + tpb - 1) / tpb;
-                wsum += (double)nbatch[i] * (descs[i].L - 1);
-            }
-            int64_t acc = 0;
-            for (size_t i = 0; i < descs.size(); ++i) {
-                int64_t n = (int64_t)ceil(target * ((double)nbatch[i] * (descs[i].L - 1)) / wsum);
-                n = n < 1 ? 1 : (n > nbatch[i] ? nbatch[i] : n);
-                acc += n;
-                l.a.blk_end[i] = (int32_t)acc;
-            }
-            l.grid = (int)acc;
+            // at most as many blocks as the free part of the partial-sum buffer has rows
+            const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NP + 1)), descs, tpb, l.a.blk_end);
+            if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
+            l.grid = (int)sg;
             if (poff + (size_t)l.grid * (NP + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
             l.a.desc = ctx->d_desc + doff;
             l.a.ndesc = (int32_t)descs.size();

@@ -553,16 +553,23 @@ struct DevLauncher {
 
     bool launch_ptr(const void* kp)
     {
+        if (plan(kp)) enqueue(kp);
+        return true;
+    }
+
+    // Occupancy and grid split of kernel kp: sets occ, grid and a.blk_end (false + herr on failure).
+    bool plan(const void* kp)
+    {
         auto key = std::make_pair(kp, std::make_pair(threads, lds));
         auto it = ctx->occ_cache.find(key);
         if (it == ctx->occ_cache.end()) {
             if (lds > 64 * 1024) {
                 herr = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (herr != hipSuccess) return true;
+                if (herr != hipSuccess) return false;
             }
             int o = 0;
             herr = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds);
-            if (herr != hipSuccess) return true;
+            if (herr != hipSuccess) return false;
             it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
         }
         occ = it->second;
@@ -572,27 +579,29 @@ struct DevLauncher {
         // dispatcher backfills as blocks retire.
         const int nb = (int)descs.size();
         double target = (double)occ * ctx->n_cu * ctx->oversub;
-        std::vector<int64_t> nbatch(nb);
-        double wsum = 0.0;
         int64_t nbsum = 0;
-        for (int i = 0; i < nb; ++i) {
-            nbatch[i] = (descs[i].N + tracks_per_block - 1) / tracks_per_block;
-            wsum += (double)nbatch[i] * (descs[i].L - 1);
-            nbsum += nbatch[i];
-        }
+        for (int i = 0; i < nb; ++i) nbsum += (descs[i].N + tracks_per_block - 1) / tracks_per_block;
         // small launches: a block should still walk >= 4 batches (its fixed costs - tables, staging set-up, final reduction - are about
         // one batch's worth), but never fewer blocks than fill the chip once.  125 000 x 30 (the 8-way shard of the headline dataset):
         // 8 generations 0.399 ms, 4 generations 0.389 ms, 1 generation 0.423 ms (r04, same box)
         if (!ctx->oversub_forced) target = std::max((double)occ * ctx->n_cu, std::min(target, (double)nbsum / 4.0));
         if (max_blocks > 0.0) target = std::max((double)nb, std::min(target, max_blocks));
-        int64_t acc = 0;
-        for (int i = 0; i < nb; ++i) {
-            int64_t n = (int64_t)ceil(target * ((double)nbatch[i] * (descs[i].L - 1)) / wsum);
-            n = n < 1 ? 1 : (n > nbatch[i] ? nbatch[i] : n);
-            acc += n;
-            a.blk_end[i] = (int32_t)acc;
+        // hard bound: the partial-sum slots of a launch (xt_max_grid) and the scratch budget, if any
+        int64_t cap = (int64_t)xt_max_grid(ctx);
+        if (max_blocks > 0.0) cap = std::min(cap, (int64_t)max_blocks);
+        const int64_t g = xt_split_descs(target, cap, descs, tracks_per_block, a.blk_end);
+        if (g < 0) {
+            herr = hipErrorInvalidConfiguration;
+            return false;
         }
-        grid = (int)acc;
+        grid = (int)g;
+        return true;
+    }
+
+    // Descriptor upload (when they changed) and the launch of kp on the grid of plan().
+    void enqueue(const void* kp)
+    {
+        const int nb = (int)descs.size();
         // the descriptors only change when the buckets (or the per-track / posterior outputs) do: keep a host shadow of the device table
         // and skip the copy when it already holds them (one dispatch less per evaluation in a fit)
         bool same = !ctx->no_fused && ctx->desc_shadow.size() >= desc_off + (size_t)nb &&
@@ -600,15 +609,15 @@ struct DevLauncher {
         if (!same) {
             if (ctx->blob_inline) {  // no blob slot guards this half of the staging area: wait for whatever still reads it
                 herr = hipStreamSynchronize(ctx->stream);
-                if (herr != hipSuccess) return true;
+                if (herr != hipSuccess) return;
             }
             memcpy(ctx->h_desc + desc_off, descs.data(), nb * sizeof(XtBucketDesc));
             herr = hipMemcpyAsync(ctx->d_desc + desc_off, ctx->h_desc + desc_off, nb * sizeof(XtBucketDesc), hipMemcpyHostToDevice, ctx->stream);
-            if (herr != hipSuccess) return true;
+            if (herr != hipSuccess) return;
             if (!ctx->blob_inline) {
                 // the staging half is reusable once this copy is done too: move the slot's guard event behind it
                 herr = hipEventRecord(ctx->ev_blob[(ctx->blob_turn - 1u) & 1u], ctx->stream);
-                if (herr != hipSuccess) return true;
+                if (herr != hipSuccess) return;
             }
             if (ctx->desc_shadow.size() < desc_off + (size_t)nb) ctx->desc_shadow.resize(desc_off + (size_t)nb);
             memcpy(ctx->desc_shadow.data() + desc_off, descs.data(), nb * sizeof(XtBucketDesc));
@@ -618,7 +627,6 @@ struct DevLauncher {
         void* kargs[2] = {(void*)&a, extra_arg};
         herr = hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream);
         if (herr == hipSuccess) herr = hipGetLastError();
-        return true;
     }
 };
 
@@ -693,17 +701,8 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
         const size_t per_block = (size_t)bargs.ws_stride * sizeof(double) * NW;
         const size_t maxb = std::max<size_t>(1, (budget_mb << 20) / per_block);
         if (maxb < bks.size()) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "n_states^frame_len sequences per track: the state of one workgroup per bucket exceeds the scratch budget (EXTRACK_BIG_WS_MB)");
+        // the grid never exceeds max_blocks (xt_split_blocks); the scratch is reserved for the grid actually launched, below
         l.max_blocks = (double)std::min<size_t>(maxb, (size_t)ctx->n_cu * 8);
-        const size_t need = (size_t)l.max_blocks * NW * (size_t)bargs.ws_stride + 64;
-        if (need > ctx->big_ws_cap) {
-            XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_big_ws) (void)hipFree(ctx->d_big_ws);
-            ctx->d_big_ws = nullptr;
-            ctx->big_ws_cap = 0;
-            XT_HIP(ctx, hipMalloc(&ctx->d_big_ws, need * sizeof(double)));
-            ctx->big_ws_cap = need;
-        }
-        bargs.ws = ctx->d_big_ws;
         l.extra_arg = (void*)&bargs;
     }
     l.threads = threads;
@@ -767,7 +766,21 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     bool ok;
     if (big) {
         const void* kp = xt_big_kernel_dk(D, K, preds);
-        ok = kp != nullptr && l.launch_ptr(kp);
+        ok = kp != nullptr;
+        if (ok && l.plan(kp)) {
+            // one ws_stride region per wavefront of the launched grid (xt_big_body indexes ws by blockIdx * NW + wave)
+            const size_t need = (size_t)l.grid * (threads / 64) * (size_t)bargs.ws_stride + 64;
+            if (need > ctx->big_ws_cap) {
+                XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                if (ctx->d_big_ws) (void)hipFree(ctx->d_big_ws);
+                ctx->d_big_ws = nullptr;
+                ctx->big_ws_cap = 0;
+                XT_HIP(ctx, hipMalloc(&ctx->d_big_ws, need * sizeof(double)));
+                ctx->big_ws_cap = need;
+            }
+            bargs.ws = ctx->d_big_ws;
+            l.enqueue(kp);
+        }
     } else {
         ok = fast2 ? xt_dispatch_f2(c.F, D, K, l) : (entry ? xt_dispatch_entry(xt_entry_gp(c.G), D, K, l) : xt_dispatch(c.G, D, K, preds, l));
     }

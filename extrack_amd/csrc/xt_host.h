@@ -16,6 +16,7 @@
 
 #include "../../include/extrack_hip.h"
 #include "xt_kernel.h"
+#include "xt_launch_split.h"
 #include "xt_tables.h"
 #include "xt_th.h"
 
@@ -382,6 +383,17 @@ int xt_prepare_config(extrack_ctx* ctx, const extrack_model* m);         // digi
 int xt_reserve_partials(extrack_ctx* ctx, size_t n);
 size_t xt_desc_base(const extrack_ctx* ctx);
 size_t xt_max_grid(const extrack_ctx* ctx);
+// xt_split_blocks (xt_launch_split.h) over bucket descriptors: blocks per bucket -> blk_end, returns the grid (<= cap) or -1
+inline int64_t xt_split_descs(double target, int64_t cap, const std::vector<XtBucketDesc>& descs, int tracks_per_block, int32_t* blk_end)
+{
+    std::vector<int64_t> N(descs.size());
+    std::vector<int32_t> L(descs.size());
+    for (size_t i = 0; i < descs.size(); ++i) {
+        N[i] = descs[i].N;
+        L[i] = descs[i].L;
+    }
+    return xt_split_blocks(target, cap, (int)descs.size(), N.data(), L.data(), tracks_per_block, blk_end);
+}
 __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, double* __restrict__ out);
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers

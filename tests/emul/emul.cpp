@@ -26,6 +26,7 @@
 #include "../../extrack_amd/csrc/xt_thgrad.h"
 #include "../../extrack_amd/csrc/xt_thgrad2.h"
 #include "../../extrack_amd/csrc/xt_big.h"
+#include "../../extrack_amd/csrc/xt_launch_split.h"
 
 struct EmulLauncher {
     XtKernelArgs a;
@@ -338,6 +339,102 @@ extern "C" int xt_emul_run_multi(int nbuckets, const double** tracks, const long
     return 0;
 }
 
+
+// The launcher's grid split (csrc/xt_launch_split.h), as the library compiles it.
+extern "C" long long xt_emul_split_blocks(double target, long long cap, int nb, const long long* N, const int* L, int tracks_per_block,
+                                          int* blk_end)
+{
+    std::vector<int64_t> n(N, N + (nb > 0 ? nb : 0));
+    std::vector<int32_t> l(L, L + (nb > 0 ? nb : 0));
+    return xt_split_blocks(target, cap, nb, n.data(), l.data(), tracks_per_block, (int32_t*)blk_end);
+}
+
+// Several length buckets served by ONE emulated launch of the global-state body (csrc/xt_big.h), the way xt_launch_group launches it: grid
+// from xt_split_blocks(target, cap, ...) (or the explicit blocks_per_bucket when given), scratch for exactly cap blocks of NW wavefront
+// regions followed by a guard tail filled with a sentinel bit pattern.  The allocation is long enough for whatever grid runs (grid > cap
+// only with explicit counts), so the body never leaves it; info[1] reports whether the tail past cap blocks is still intact.
+// info [4]: grid, guard intact, tracks per block, ws_stride.
+extern "C" int xt_emul_big_multi(int nbuckets, const double** tracks, const long long* Ns, const int* Ls, int D, int S, int NS, int F,
+                                 int max_len, int min_len, int locerr_dims, const double* locerr, double pBL, const double* ds,
+                                 const double* Fs, const double* TrMat, const double* p_stay, double target, long long cap,
+                                 const int* blocks_per_bucket, int preds, double** ll_out, double** preds_out, double* total, int* info)
+{
+    if (nbuckets < 1 || nbuckets > XT_MAX_BUCKETS) return -4;
+    XtConfig cfg;
+    if (!xt_build_config(S, NS, F, cfg).empty()) return -1;
+    XtModelHost m{S, NS, locerr_dims, {0, 0, 0}, 0.0, 0.0, pBL, ds, Fs, TrMat, p_stay};
+    for (int k = 0; k < 3; ++k) m.locerr[k] = locerr[k < locerr_dims ? k : 0];
+    std::vector<double> blob;
+    xt_build_blob(m, cfg, blob);
+    const int K = locerr_dims, NW = 2, tpb = 64 * NW;
+    XtKernelArgs a;
+    memset(&a, 0, sizeof(a));
+    xt_fill_args_from_config(cfg, a);
+    std::vector<XtBucketDesc> descs(nbuckets);
+    std::vector<int64_t> N(nbuckets);
+    std::vector<int32_t> L(nbuckets);
+    for (int i = 0; i < nbuckets; ++i) {
+        descs[i] = XtBucketDesc{tracks[i], nullptr, ll_out ? ll_out[i] : nullptr, preds ? preds_out[i] : nullptr, Ns[i], Ls[i],
+                                Ls[i] != max_len ? 1 : 0, -(double)(Ls[i] - 1) * D * 0.5 * XT_LOG2PI};
+        N[i] = Ns[i];
+        L[i] = Ls[i];
+    }
+    int64_t grid = 0;
+    if (blocks_per_bucket) {
+        for (int i = 0; i < nbuckets; ++i) {
+            if (blocks_per_bucket[i] < 1) return -5;
+            grid += blocks_per_bucket[i];
+            a.blk_end[i] = (int32_t)grid;
+        }
+    } else {
+        grid = xt_split_blocks(target, cap, nbuckets, N.data(), L.data(), tpb, a.blk_end);
+        if (grid < 0) return -5;
+    }
+    XtBigArgs ba;
+    ba.ws_stride = xt_big_ws_doubles(cfg.E, D, K);
+    const uint64_t sentinel = 0x7ff8dead5e47e1a1ull;  // a quiet NaN with a payload no computation produces
+    const size_t inside = (size_t)cap * NW * ba.ws_stride;
+    const size_t total_len = (size_t)std::max<int64_t>(grid, cap) * NW * ba.ws_stride + (size_t)NW * ba.ws_stride;
+    std::vector<double> ws(total_len, xt_emul_poison() ? NAN : 0.0);
+    for (size_t i = inside; i < total_len; ++i) memcpy(&ws[i], &sentinel, 8);
+    ba.ws = ws.data();
+    std::vector<double> partials(grid, 0.0);
+    a.desc = descs.data();
+    a.ndesc = nbuckets;
+    a.blob = blob.data();
+    a.base_tab = cfg.base_tab.data();
+    a.off_tab = cfg.off_tab.data();
+    a.partials = partials.data();
+    a.TPB = tpb;
+    a.min_len = min_len;
+    a.locerr_mode = 0;
+    a.KS = 1;
+    const size_t ldsd = (size_t)((xt_tab_doubles(S, cfg.G) + 1) & ~1) + tpb;
+#define XT_BIG_RUN(DD, KK)                                                                                                \
+    th_emul_blocks((int)grid, tpb, ldsd, [&](HostCtx& cx) {                                                                \
+        if (preds) xt_big_body<DD, KK, true>(a, ba, cx);                                                                   \
+        else xt_big_body<DD, KK, false>(a, ba, cx);                                                                        \
+    })
+    if (D == 1 && K == 1) XT_BIG_RUN(1, 1);
+    else if (D == 2 && K == 1) XT_BIG_RUN(2, 1);
+    else if (D == 2 && K == 2) XT_BIG_RUN(2, 2);
+    else if (D == 3 && K == 1) XT_BIG_RUN(3, 1);
+    else if (D == 3 && K == 3) XT_BIG_RUN(3, 3);
+    else return -3;
+#undef XT_BIG_RUN
+    bool intact = true;
+    for (size_t i = inside; i < total_len && intact; ++i) intact = memcmp(&ws[i], &sentinel, 8) == 0;
+    double s = 0.0;
+    for (double p : partials) s += p;
+    if (total) *total = s;
+    if (info) {
+        info[0] = (int)grid;
+        info[1] = intact ? 1 : 0;
+        info[2] = tpb;
+        info[3] = (int)ba.ws_stride;
+    }
+    return 0;
+}
 
 // Per-track time steps for the next xt_emul_th_run / xt_emul_th_predict call: dt [N][L] and one p_stay table [G] per chunk.
 static const double* g_th_dt = nullptr;

@@ -14,7 +14,7 @@ def lib():
         so = os.path.join(HERE, "libxt_emul.so")
         src = os.path.join(HERE, "emul.cpp")
         hdrs = [os.path.join(HERE, "..", "..", "extrack_amd", "csrc", h) for h in ("xt_kernel.h", "xt_math.h", "xt_tables.h", "xt_dispatch.h", "xt_th.h", "xt_entry.h", "xt_fast2.h", "xt_grad.h",
-                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h")]
+                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h", "xt_launch_split.h")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src, os.path.join(HERE, "emul_r2.cpp"), os.path.join(HERE, "emul_gradr.cpp"), os.path.join(HERE, "emul_rev.cpp"), os.path.join(HERE, "emul_ctx.h")] + hdrs):
             import subprocess
             units = ["emul.cpp", "emul_r2.cpp", "emul_gradr.cpp", "emul_rev.cpp"]  # compiled side by side: emul_r2.cpp unrolls the whole step loop per instance
@@ -100,6 +100,46 @@ def run_multi(buckets, locerr, ds, Fs, T, pBL, p_stay, ns, F, min_len, max_len, 
     if rc != 0:
         raise RuntimeError("emul multi rc=%d" % rc)
     return outs, tot.value
+
+
+def split_blocks(target, cap, Ns, Ls, tracks_per_block):
+    """The launcher's grid split (csrc/xt_launch_split.h): (grid or -1, blocks per bucket)."""
+    nb = len(Ns)
+    be = (C.c_int * max(nb, 1))()
+    f = lib().xt_emul_split_blocks
+    f.restype = C.c_longlong
+    g = f(C.c_double(target), C.c_longlong(cap), nb, (C.c_longlong * max(nb, 1))(*Ns), (C.c_int * max(nb, 1))(*Ls), int(tracks_per_block), be)
+    end = np.array(be[:nb], np.int64)
+    return int(g), np.diff(np.concatenate([[0], end])) if g >= 0 else None
+
+
+def run_big_multi(buckets, locerr, ds, Fs, T, pBL, p_stay, ns, F, min_len, max_len, target, cap, blocks_per_bucket=None, preds=False):
+    """Several buckets through ONE emulated launch of the global-state body (csrc/xt_big.h) with a guarded scratch of cap blocks.
+    Returns (per-track lists, posterior lists or None, total, info) with info = {grid, guard_intact, tracks_per_block, ws_stride}."""
+    nb = len(buckets)
+    bk = [np.ascontiguousarray(b, float) for b in buckets]
+    D = bk[0].shape[2]
+    S = len(ds)
+    le = np.zeros(3)
+    locerr = np.atleast_1d(np.asarray(locerr, float)).ravel()
+    le[:len(locerr)] = locerr
+    outs = [np.zeros(len(b)) for b in bk]
+    prs = [np.full((len(b), b.shape[1], S), -1.0) for b in bk] if preds else None
+    PD = C.POINTER(C.c_double)
+    tr = (PD * nb)(*[dp(b) for b in bk])
+    lo = (PD * nb)(*[dp(o) for o in outs])
+    po = (PD * nb)(*[dp(p) for p in prs]) if preds else None
+    Ns = (C.c_longlong * nb)(*[len(b) for b in bk])
+    Ls = (C.c_int * nb)(*[b.shape[1] for b in bk])
+    bp = (C.c_int * nb)(*blocks_per_bucket) if blocks_per_bucket is not None else None
+    tot = C.c_double(0)
+    info = (C.c_int * 4)()
+    ds, Fs, T, p_stay = [np.ascontiguousarray(x, float) for x in (ds, Fs, T, p_stay)]
+    rc = lib().xt_emul_big_multi(nb, tr, Ns, Ls, D, S, ns, F, int(max_len), int(min_len), len(locerr), dp(le), C.c_double(pBL), dp(ds),
+                                 dp(Fs), dp(T), dp(p_stay), C.c_double(target), C.c_longlong(cap), bp, int(preds), lo, po, C.byref(tot), info)
+    if rc != 0:
+        raise RuntimeError("emul big multi rc=%d" % rc)
+    return outs, prs, tot.value, dict(zip(("grid", "guard_intact", "tracks_per_block", "ws_stride"), list(info)))
 
 
 def run_th(Cs, LE, ds, Fs, T, pBL, isBL, p_stay, ns, F, min_len, threshold, max_nb, chunk=2000, capE=256, TT=8, threads=64, nblocks=2,

@@ -228,6 +228,108 @@ def test_global_state_kernel_forced_on_ordinary_models(monkeypatch):
     assert max(np.abs(pr[k] - pro[k]).max() for k in tracks) < 1e-9
 
 
+
+def _big_budget_blocks(S, F, D, K, budget_mb, n_cu):
+    """Blocks of the global-state kernel's scratch budget, restated from xt_launch_group: one region of xt_big_ws_doubles(E, D, K) doubles
+    per wavefront, NW = 4 wavefronts per block, at most 8 blocks per CU."""
+    E = S ** F
+    ws = E * 64 * (1 + D + K) + (E * 64 + 1) // 2
+    return min(max(1, (budget_mb << 20) // (ws * 8 * 4)), n_cu * 8)
+
+
+def _per_bucket_ll(buckets, model_of, min_len, max_len):
+    """Per-track LL of every bucket evaluated alone (a single-bucket launch), with the dataset-global min / max length."""
+    from extrack_amd import tracking as T
+    out = []
+    for b in buckets:
+        ts = T.TrackSet([b], min_len=min_len, max_len=max_len)
+        try:
+            out.append(ts.loglik(model_of(ts), per_track=True)[1])
+        finally:
+            ts.close()
+    return out
+
+
+def test_global_state_kernel_multi_bucket_split_within_small_budget(monkeypatch):
+    """Forced global-state kernel with a 16 MiB scratch budget on three length buckets (3000 / 4100 / 5200 tracks of lengths 9 / 14 / 23,
+    2 states, frame_len 6): the proportional split asks for 4 + 8 + 17 blocks where the budget holds 28.  The launched grid stays within
+    the budget; per-track LL and posteriors equal the LDS kernels'; 100 tracks per bucket against the oracle; the total equals the sum of
+    the buckets evaluated one at a time."""
+    from extrack_amd import synth, tracking as T
+    from oracle import oracle_np as O
+    vals = dict(D0=1e-3, D1=0.25, LocErr=0.02, F0=0.6, F1=0.4, p01=0.1, p10=0.1, pBL=0.1)
+    p = _params(vals)
+    Tm = [[.9, .1], [.1, .9]]
+    Ns, Ls = (3000, 4100, 5200), (9, 14, 23)
+    buckets = [synth.brownian_tracks(n, L, [0.0, 0.25], Tm, [.6, .4], seed=40 + i) for i, (n, L) in enumerate(zip(Ns, Ls))]
+    model_of = lambda ts: T._objective_model(p, ts, 0.02, [1], None, 2, 1, 6, 1)
+    monkeypatch.delenv("EXTRACK_FORCE_BIG", raising=False)
+    ts = T.TrackSet(buckets)
+    try:
+        tot_lds, per_lds = ts.loglik(model_of(ts), per_track=True)
+        monkeypatch.setenv("EXTRACK_FORCE_BIG", "1")
+        monkeypatch.setenv("EXTRACK_BIG_WS_MB", "16")
+        tot, per = ts.loglik(model_of(ts), per_track=True)
+        info = ts.ctx.last_launch_info()
+    finally:
+        ts.close()
+    cap = _big_budget_blocks(2, 6, 2, 1, 16, info["compute_units"])
+    assert info["tracks_per_block"] == 256 and info["blocks"] <= cap, (info, cap)
+    if info["compute_units"] == 256:
+        assert info["blocks"] == cap == 28  # the budget binds: the proportional split (4 + 8 + 17) is trimmed to it
+    assert np.abs(per - per_lds).max() < TOL_LL
+    assert abs(tot - per.sum()) < 1e-12 * abs(tot)
+    alone = _per_bucket_ll(buckets, model_of, min(Ls), max(Ls))
+    assert abs(tot - sum(a.sum() for a in alone)) < 1e-12 * abs(tot)
+    _, ds, Fs, TrMat, pBL = T.extract_params(p, 0.02, 2, 1)
+    o = 0
+    for b, a in zip(buckets, alone):
+        assert np.abs(per[o:o + len(b)] - a).max() < TOL_LL
+        ref = O.proba_cs(b[:100], np.array([[[0.02]]]), ds, Fs, TrMat, pBL, int(b.shape[1] != max(Ls)), [1], 1, 6, min(Ls))
+        assert np.abs(per[o:o + 100] - ref).max() < TOL_LL
+        o += len(b)
+    tracks = {str(L): b for L, b in zip(Ls, buckets)}
+    pr = T.predict_Bs(tracks, 0.02, p, cell_dims=[1], nb_states=2, frame_len=6)
+    monkeypatch.delenv("EXTRACK_FORCE_BIG")
+    pr_lds = T.predict_Bs(tracks, 0.02, p, cell_dims=[1], nb_states=2, frame_len=6)
+    assert max(np.abs(pr[k] - pr_lds[k]).max() for k in tracks) < TOL_PRED
+
+
+def test_global_state_kernel_default_budget_binds_on_five_states():
+    """5 states at the reference's default frame_len 6 (15 625 sequences per track, natively the global-state kernel): 3 x 30 000 tracks of
+    lengths 7 / 8 / 10, where the proportional split asks for one block more than the 32 GiB default budget holds.  The grid stays within
+    the budget; per-track LL equals each bucket evaluated alone (1e-12); 4 tracks per bucket against the oracle."""
+    from extrack_amd import synth, tracking as T
+    from oracle import oracle_np as O
+    S, F = 5, 6
+    Ds = np.array([0.0, 0.01, 0.05, 0.1, 0.3])
+    Tm = np.full((S, S), 0.04)
+    Tm[np.arange(S), np.arange(S)] = 1 - 0.04 * (S - 1)
+    Fs = np.full(S, 1.0 / S)
+    ds = np.sqrt(2 * Ds * 0.02) + 1e-3
+    LE = np.array([[[0.02]]])
+    Ls = (7, 8, 10)
+    buckets = [synth.brownian_tracks(30000, L, Ds, Tm, Fs, seed=50 + L) for L in Ls]
+    model_of = lambda ts: ts.make_model(LE, ds, Fs, Tm, 0.1, [1.0], 1, F)
+    ts = T.TrackSet(buckets)
+    try:
+        tot, per = ts.loglik(model_of(ts), per_track=True)
+        info = ts.ctx.last_launch_info()
+    finally:
+        ts.close()
+    cap = _big_budget_blocks(S, F, 2, 1, 32 * 1024, info["compute_units"])
+    assert info["tracks_per_block"] == 256 and info["blocks"] <= cap, (info, cap)
+    if info["compute_units"] == 256:
+        assert info["blocks"] == cap == 238  # the budget binds: the proportional split (65 + 76 + 98) is trimmed to it
+    assert np.all(np.isfinite(per)) and abs(tot - per.sum()) < 1e-12 * abs(tot)
+    alone = _per_bucket_ll(buckets, model_of, min(Ls), max(Ls))
+    o = 0
+    for b, a in zip(buckets, alone):
+        assert np.abs(per[o:o + len(b)] - a).max() < 1e-12
+        ref = O.proba_cs(b[:4], LE, ds, Fs, Tm, 0.1, int(b.shape[1] != max(Ls)), [1.0], 1, F, min(Ls))
+        assert np.abs(per[o:o + 4] - ref).max() < TOL_LL
+        o += len(b)
+
 def test_full_size_properties():
     """BASELINE.json configs[1] at full size (1e6 x 30): size-independent properties.
     (a) total == sum of per-track values (rel 1e-12); (b) permutation invariance of the total;
