@@ -189,10 +189,11 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 
     // ---- tangents (formulas: header of xt_grad.h), all on normalised quantities; first the primal factors they share (kept few:
     // with 7-8 directions x 16 VGPRs of tangent state the step must fit the rest into ~100 registers)
-    double a0 = 0.0, cm[D], cu[K], dn[D], Aq[2][K], rq[2][K];
+    double a0 = 0.0, a1 = 0.0, cm[D], cu[K], dn[D], Aq[2][K], rq[2][K];
     if (NP > 0) {
         a0 = w0 * rW;  // a0 = a1 = 0 for an all-zero group (rW = 1 then)
-        const double aa = a0 * (w1 * rW);
+        a1 = w1 * rW;
+        const double aa = a0 * a1;
         XT_UNROLL
         for (int d = 0; d < D; ++d) {
             cm[d] = aa * (s.m[0][d] - s.m[1][d]);
@@ -237,12 +238,15 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
             XT_UNROLL
             for (int k = 0; k < K; ++k) dl[k] = xt_at<double>(lds, tb + k * 8);
             const double del = s.rz[pp][0] - s.rz[pp][1];
-            const double R = xt_fma(a0, del, s.rz[pp][1]);
+            // R, d m_bar, d u_bar = sum a_j (.)_j as the convex combinations they are.  The shorter x_1 + a0 (x_0 - x_1) rounds at ulp(x_1):
+            // a member of negligible weight that carries a huge d log z (d log T = 1 / T along a tiny transition probability; its dm, du
+            // inherit rounding of that size) then wipes out the dominant member's tangent
+            const double R = xt_fma(a0, s.rz[pp][0], a1 * s.rz[pp][1]);
             double dmb[D], dub[K];
             XT_UNROLL
-            for (int d = 0; d < D; ++d) dmb[d] = xt_fma(cm[d], del, xt_fma(a0, s.dm[pp][0][d] - s.dm[pp][1][d], s.dm[pp][1][d]));
+            for (int d = 0; d < D; ++d) dmb[d] = xt_fma(cm[d], del, xt_fma(a0, s.dm[pp][0][d], a1 * s.dm[pp][1][d]));
             XT_UNROLL
-            for (int k = 0; k < K; ++k) dub[k] = xt_fma(cu[k], del, xt_fma(a0, s.du[pp][0][k] - s.du[pp][1][k], s.du[pp][1][k]));
+            for (int k = 0; k < K; ++k) dub[k] = xt_fma(cu[k], del, xt_fma(a0, s.du[pp][0][k], a1 * s.du[pp][1][k]));
             double hd[K];  // -1/2 d |c - m_bar|^2 = sum_d (c - m_bar)_d d m_bar_d (per dim when K == D)
             if (K == 1) {
                 hd[0] = 0.0;

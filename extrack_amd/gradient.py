@@ -175,7 +175,8 @@ def analytic_support(params, names):
 
 def objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, frame_len, Matrix_type=1, comm=None, names=None,
                            threshold_fusion=None):
-    """(-sum LL, d(-sum LL)/d(free parameter VALUES)) at ``params`` on the TrackSet ``ts``; (+inf, zeros) for invalid parameters.
+    """(-sum LL, d(-sum LL)/d(free parameter VALUES)) at ``params`` on the TrackSet ``ts``; (+inf, zeros) for invalid parameters and for
+    a NaN objective (a NaN position or localisation error poisons its track's LL in the kernels), as ``cum_Proba_Cs`` maps NaN to +inf.
     ``comm``: extrack_amd.distributed.Comm - the (1 + nvar) vector is all-reduced over the ranks.
     ``threshold_fusion``: None = the fixed-window objective; (threshold, max_nb_states, chunk) = the threshold-fusion objective of
     extrack/tracking.py:427-743 and its gradient at the frozen plan of this evaluation (extrack_loglik_th_grad)."""
@@ -211,4 +212,6 @@ def objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, fr
     else:
         v = np.zeros(1 + len(names))
     ll, g = float(v[0]), v[1:]
+    if np.isnan(ll):
+        return np.inf, np.zeros(len(names))
     return -ll, -np.asarray(g)
