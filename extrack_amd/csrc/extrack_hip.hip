@@ -729,7 +729,7 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
                 if (lo != lo || hi != hi) break;
             }
         }
-        l.a.well_scaled = (ctx->blob_host.size() > 8 && xt_model_well_scaled(ctx->blob_host, lo, hi)) ? 1 : 0;
+        l.a.well_scaled = ctx->blob_host.size() > 8 ? xt_launch_scaling(ctx->blob_host, lo, hi, m->locerr_mode == 0 && K == 1) : 0;
     }
     l.desc_off = desc_off;
     for (XtBucket* b : bks) {

@@ -55,6 +55,14 @@ XT_HD int xt_r2_pos0(int NP) { return XT_R2_TAN0 + NP * XT_R2_TB * 8; }
 XT_HD int xt_r2_acc0(int NP, int D, int KS, int tpw) { return xt_r2_pos0(NP) + XT_F2_WAVES * tpw * XT_F2_CHUNK * (D + KS) * 8; }
 XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw) { return xt_r2_acc0(NP, D, KS, tpw) + XT_F2_WAVES * 8 * (NP + 3) * 8; }
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
+// Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
+// ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2), 2 l2} and lnT'[v][prev][q] = ln TAB[v][prev][q] - D/2 ln l2, v = 0 (T), 1 (T * stay)
+// - at a fixed distance from the entry of table v, so that the step reaches it from the same `tab + [prev][q]` address.
+#define XT_R2_GC_OFF 800
+#define XT_R2_LNT_OFF 960
+#define XT_R2_LNT_REL (XT_R2_LNT_OFF - XT_R2_TAB0)
+static_assert(XT_R2_GC_OFF >= (XT_BLOB_HDR + XT_NTAB * 4 + 64) * 8 && XT_R2_GC_OFF + 16 <= XT_F2_NAN_OFF, "g-form constants overlap the blob / the NaN flags");
+static_assert(XT_R2_LNT_OFF >= XT_F2_NAN_OFF + XT_F2_WAVES * 8 * 4 && XT_R2_LNT_OFF + 64 <= XT_F2_EXPB_OFF, "lnT' overlaps the NaN flags / the exp table");
 
 static inline bool xt_use_reg2(int S, int NS, int F) { return S == 2 && NS == 1 && F >= 4 && F <= 7; }
 
@@ -294,6 +302,96 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
     }
 }
 
+// The same step in "g-form": scalar variance (K == 1), ONE global localisation variance l2 > 0, likelihood only, zero-free and lazily
+// re-normalised (xt_r2_step<.., ZF = true, LAZY = true> is what it replaces; FIRST as there).  Every per-child quantity is a function of
+// the one ratio g_q = l2 / den_q in (0, 1]:
+//     tt_q = 1 - g_q           =>  m_q = c - (c - m_bar) g_q                       (one fma per dimension)
+//     u_q = l2 (1 - g_q)       =>  the members carry v = l2 + u:  v_q = 2 l2 - l2 g_q,  W den_q = Ws d2_q + V  (no l2 + d2 add)
+//     den_q^(-D/2) = (g_q / l2)^(D/2),  -|c - m_bar|^2 / (2 den_q) = A g_q  with  A = -|c - m_bar|^2 / (2 l2)
+//     weight_q = Wm g_q^(D/2) exp(A g_q + lnT'[prev][q]),  lnT' = ln T - D/2 ln l2   (table built per workgroup: no T multiply, no gf)
+// The shared reciprocal R = 1 / (Ws Dq0 Dq1) stays: 1 / W = R Dq0 Dq1 and g_q = (R Ws^2 l2) Dq[1 - q].  61 fp64 operations for D = 2
+// against 73 of the general form.  The exponential's argument may be POSITIVE here (up to D/2 ln(1 / l2) = 41.4 at l2 = 1e-12, D = 3): the
+// bit extraction of xt_f2_exp_bits holds for either sign (two's complement of n in the mantissa field: j = n mod 1024, e = floor(n / 1024)
+// for |n| < 2^41; the magic-number rounding and the two-part reduction do not depend on the sign either), so xt_exp_tab_x2 is used as it
+// is, with its clamp of each argument from below.  (Clamping the shared factor A once instead is NOT equivalent: A is the squared jump in
+// units of l2, not of den - at l2 = 1e-10 an everyday displacement of 0.05 gives A = -1.3e7 while A g_q is of order -1.)
+// Lazy re-normalisation range: a child's mantissa is Wm g^(D/2) tj p with g = l2 / den in [1e-16, 1] (well-scaled bounds: l2 >= 1e-12,
+// den <= 1e4) and tj p in [1, 2): three un-normalised steps (merges double) stay within [1e-72, 64]; the products of a step are then
+// W^3 den^2 >= 1e-240 and R Ws^2 l2 <= 1e264 * 1e4 - the transition weight and l2^(-D/2) live in the integer exponent.
+template <int F, int D, int H, bool FIRST = false, class Ctx>
+XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, int tab, const double* c)
+{
+    constexpr int NGB = F - 1;
+    constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
+    const int lane = xt_opaque(cx.lane());
+    const int prev = (lane >> PB) & 1;
+    const int qa = Ctx::template pair_natural<XB>() ? 0 : (lane >> XB) & 1;
+    const int io[2] = {(prev * 2 + qa) * 8, (prev * 2 + (qa ^ 1)) * 8};
+    double TD2[2], LT[2];
+    XT_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        TD2[q] = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + io[q]);
+        LT[q] = xt_at<double>(lds, tab + XT_R2_LNT_REL + io[q]);
+    }
+    const double l2 = xt_at<double>(lds, 0), nh = xt_at<double>(lds, XT_R2_GC_OFF), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
+
+    // ---- merge (members carry v = l2 + u)
+    const int e0 = s.e[0], e1 = s.e[1];
+    const int emax = e0 > e1 ? e0 : e1;
+    const double w0 = FIRST ? 1.0 : xt_ldexp(s.z[0], e0 - emax), w1 = FIRST ? 0.0 : xt_ldexp(s.z[1], e1 - emax);
+    const double Ws = FIRST ? 1.0 : w0 + w1;
+    double M[D];
+    XT_UNROLL
+    for (int d = 0; d < D; ++d) M[d] = FIRST ? s.m[0][d] : xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
+    const double V = FIRST ? s.u[0][0] : xt_fma(w1, s.u[1][0], w0 * s.u[0][0]);
+    constexpr bool RN = (H % XT_F2_RENORM) == 0;
+    const double Wm = FIRST ? s.z[0] : (RN ? xt_frexp_mant(Ws) : Ws);
+    const int We = FIRST ? e0 : (RN ? emax + xt_frexp_exp(Ws) : emax);
+
+    // ---- the shared reciprocal, g_q
+    const double Dq0 = xt_fma(Ws, TD2[0], V), Dq1 = xt_fma(Ws, TD2[1], V);
+    const double d01 = Dq0 * Dq1;
+    const double R = xt_rcp(Ws * d01);
+    const double rW = FIRST ? 1.0 : R * d01;
+    const double G = R * (Ws * (Ws * l2));
+    const double g[2] = {G * Dq1, G * Dq0};
+    double dn[D], dsq = 0.0;
+    XT_UNROLL
+    for (int d = 0; d < D; ++d) {
+        dn[d] = xt_fma(c[d], Ws, -M[d]) * rW;  // c - m_bar
+        dsq = xt_fma(dn[d], dn[d], dsq);
+    }
+    const double A = dsq * nh;
+    double p[2];
+    int j[2], n[2];
+    xt_exp_tab_x2(xt_fma(A, g[0], LT[0]), xt_fma(A, g[1], LT[1]), p[0], p[1], j[0], j[1], n[0], n[1]);
+    double nz[2], nm[2][D], nv[2];
+    int ne[2];
+    XT_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        const int en = We + n[q];
+        const double tj = xt_at<double>(lds, XT_F2_EXPB_OFF + j[q] * 8);
+        nz[q] = (Wm * xt_pow_half<D>(g[q])) * (tj * p[q]);
+        ne[q] = en > XT_EMIN ? en : XT_EMIN;
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(-dn[d], g[q], c[d]);
+        nv[q] = xt_fma(-l2, g[q], l22);
+    }
+    cx.template pair_exchange<XB>(nz[0], nz[1]);
+    cx.template pair_exchange_i32<XB>(ne[0], ne[1]);
+    XT_UNROLL
+    for (int d = 0; d < D; ++d) cx.template pair_exchange<XB>(nm[0][d], nm[1][d]);
+    cx.template pair_exchange<XB>(nv[0], nv[1]);
+    XT_UNROLL
+    for (int q = 0; q < 2; ++q) {
+        s.z[q] = nz[q];
+        s.e[q] = ne[q];
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) s.m[q][d] = nm[q][d];
+        s.u[q][0] = nv[q];
+    }
+}
+
 // all-reduce over the lanes of a track (the F - 1 group bits)
 template <int F, class Ctx>
 XT_HD double xt_r2_gsum(Ctx& cx, double v)
@@ -416,6 +514,18 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     cx.sync();
     xt_f2_check_lds_base(lds);
     xt_f2_build_exp_table(cx, lds, XT_F2_EXPB_OFF, (const double*)(lds + XT_F2_T64_OFF));  // the 1024-entry table of xt_exp_tab_x2 from the blob's 64 entries
+    // g-form steps (xt_r2_step_g): the launcher found one global localisation variance l2 >= 1e-12 in a well-scaled launch (well_scaled == 2)
+    const bool gform = NP == 0 && K == 1 && a.well_scaled == 2 && a.locerr_mode == 0;
+    if constexpr (NP == 0 && K == 1) {
+        if (gform && cx.tid() < 10) {
+            const int i = cx.tid();
+            const double l2 = smem[0];
+            if (i < 8)
+                xt_at<double>(lds, XT_R2_LNT_OFF + i * 8) = log(smem[XT_BLOB_HDR + i]) - 0.5 * D * log(l2);
+            else
+                xt_at<double>(lds, XT_R2_GC_OFF + (i - 8) * 8) = i == 8 ? -0.5 / l2 : 2.0 * l2;
+        }
+    }
     cx.sync();
     const double* hdr = smem;
 
@@ -506,6 +616,14 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
+#define XT_R2_PHASE_G(H)                                                                               \
+    if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
+        double c[D], l2[K];                                                                            \
+        getpos(t, c, l2);                                                                              \
+        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, XT_R2_TABSEL, c);                        \
+        ++t;                                                                                           \
+        ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
+    }
 #define XT_R2_PHASES(ZF_, LAZY_) \
     XT_R2_PHASE(0, ZF_, LAZY_)   \
     XT_R2_PHASE(1, ZF_, LAZY_)   \
@@ -522,6 +640,19 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 return;
             }
             // well-scaled: positions 1 .. F - 1 are done by the warm-up chain and the merge-free first step (every lane live from here on)
+            if constexpr (NP == 0 && K == 1) {
+                if (gform) {
+                    while (t <= tend2) {
+                        XT_R2_PHASE_G(0)
+                        XT_R2_PHASE_G(1)
+                        XT_R2_PHASE_G(2)
+                        XT_R2_PHASE_G(3)
+                        XT_R2_PHASE_G(4)
+                        XT_R2_PHASE_G(5)
+                    }
+                    return;
+                }
+            }
             while (t <= tend2) { XT_R2_PHASES(true, true) }
         };
 #undef XT_R2_TABSEL
@@ -540,6 +671,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
 #undef XT_R2_TABSEL
 #undef XT_R2_PHASES
+#undef XT_R2_PHASE_G
 #undef XT_R2_PHASE
 
         XtAcc tot;
@@ -590,7 +722,15 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         if (L - 2 >= F - 1) {
                             double c[D], l2[K];
                             getpos(F - 1, c, l2);
-                            xt_r2_step<F, D, K, NP, NGB - 1, true, true, VAR, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, l2);
+                            bool first_done = false;
+                            if constexpr (K == 1) {
+                                if (gform) {  // from here on the members carry v = l2 + u (until the read-out of the last position)
+                                    s.u[0][0] += l2[0];
+                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
+                                    first_done = true;
+                                }
+                            }
+                            if (!first_done) xt_r2_step<F, D, K, NP, NGB - 1, true, true, VAR, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, l2);
                             t = F;
                         } else {
                             t = L - 1 > 1 ? L - 1 : 1;
@@ -609,6 +749,9 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             // ---- last position (+ leaving / bleaching factor): reduction over (member Q, new digit q)
             double cl[D], l2l[K];
             getpos(tlast, cl, l2l);
+            if constexpr (NP == 0 && K == 1) {
+                if (gform && L - 2 >= F - 1) l2l[0] = 0.0;  // the g-form steps left v = l2 + u in the members
+            }
             const int hp = (tlast - 2 + NGB) % NGB;  // group bit of the newest digit
             const int pbit = (F == 7 || hp < 2) ? hp : hp + 1;
             const int prev = (lane >> pbit) & 1;

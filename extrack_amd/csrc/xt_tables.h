@@ -149,7 +149,9 @@ static inline void xt_build_blob(const XtModelHost& m, const XtConfig& c, std::v
     // variance in [1e-12, 1e4].  Then (a) no sequence weight
     // is ever exactly zero once the window is populated and (b) a mantissa left un-normalised for XT_F2_RENORM steps stays within
     // [1e-80, 1e55], far from where the step's products (W^3 den^2) would leave the fp64 range: the 2-state fast path then drops its
-    // zero handling and re-normalises lazily; any other model takes the fully guarded steps.
+    // zero handling and re-normalises lazily; any other model takes the fully guarded steps.  (The g-form step of xt_reg2.h keeps the
+    // transition weight and l2^(-D/2) in the integer exponent: its mantissas only pick up (l2 / den)^(D/2) in [1e-24, 1] and a factor in
+    // [1, 2) per step and stay within [1e-72, 64] - see xt_r2_step_g.)
     // The launcher (xt_model_well_scaled) combines slot 5 (fractions / weights in range) and the displacement-variance range in slots
     // 6, 7 with the range of the localisation variance - global, or from the per-peak errors seen at upload - into the kernel argument.
     bool ok = true;
@@ -169,6 +171,15 @@ static inline void xt_build_blob(const XtModelHost& m, const XtConfig& c, std::v
 static inline bool xt_model_well_scaled(const std::vector<double>& blob, double l2lo, double l2hi)
 {
     return blob[5] != 0.0 && l2lo == l2lo && l2hi == l2hi && l2lo + blob[6] >= 1e-12 && 2.0 * l2hi + blob[7] <= 1e4;
+}
+
+// The value of XtKernelArgs::well_scaled for a launch: 0 guarded steps, 1 well scaled, 2 well scaled AND the launch has ONE global
+// localisation variance l2 >= 1e-12 (l2lo == l2hi then), which the g-form step of the register-resident 2-state kernel divides by (xt_reg2.h:
+// g = l2 / den; with LocErr = 0 that is 0 / 0).  Per-dimension or per-peak errors stay at 1.
+static inline int xt_launch_scaling(const std::vector<double>& blob, double l2lo, double l2hi, bool one_global_l2)
+{
+    if (!xt_model_well_scaled(blob, l2lo, l2hi)) return 0;
+    return one_global_l2 && l2lo == l2hi && l2lo >= 1e-12 ? 2 : 1;
 }
 
 // Model tables of the threshold-fusion kernels (xt_th.h): same five [prev][.] tables and header as xt_build_blob, but the
