@@ -53,7 +53,15 @@ XT_HD int xt_r2_slot(int lane)
 #define XT_R2_MAXU 4  // uniform directions served by one launch (on top of its NP full ones)
 XT_HD int xt_r2_pos0(int NP) { return XT_R2_TAN0 + NP * XT_R2_TB * 8; }
 XT_HD int xt_r2_acc0(int NP, int D, int KS, int tpw) { return xt_r2_pos0(NP) + XT_F2_WAVES * tpw * XT_F2_CHUNK * (D + KS) * 8; }
-XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw) { return xt_r2_acc0(NP, D, KS, tpw) + XT_F2_WAVES * 8 * (NP + 3) * 8; }
+// likelihood-only launches (NP == 0), after the accumulators: the re-centring cells of the log-carried g-form step (xt_r2_step_g), one
+// 8-byte cell per lane each (an int in it) - [largest base of the track, in the cell of the track's first lane][accumulated shift of the
+// track in flight] - and per (wave, slot) a double: the shifts of the finished tracks
+#define XT_R2_RC_ARR (XT_F2_WAVES * 64 * 8)
+XT_HD int xt_r2_rc0(int D, int KS, int tpw) { return xt_r2_acc0(0, D, KS, tpw) + XT_F2_WAVES * 8 * 3 * 8; }
+XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw)
+{
+    return xt_r2_acc0(NP, D, KS, tpw) + XT_F2_WAVES * 8 * (NP + 3) * 8 + (NP == 0 ? 2 * XT_R2_RC_ARR + XT_F2_WAVES * 8 * 8 : 0);
+}
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
 // Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
 // ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2), 2 l2} and lnT'[v][prev][q] = ln TAB[v][prev][q] - D/2 ln l2, v = 0 (T), 1 (T * stay)
@@ -302,24 +310,41 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
     }
 }
 
-// The same step in "g-form": scalar variance (K == 1), ONE global localisation variance l2 > 0, likelihood only, zero-free and lazily
-// re-normalised (xt_r2_step<.., ZF = true, LAZY = true> is what it replaces; FIRST as there).  Every per-child quantity is a function of
-// the one ratio g_q = l2 / den_q in (0, 1]:
+// The same step in "g-form" with LOG-CARRIED weights: scalar variance (K == 1), ONE global localisation variance l2 > 0, likelihood only,
+// zero-free and lazily re-normalised (xt_r2_step<.., ZF = true, LAZY = true> is what it replaces; FIRST as there).  Every per-child quantity
+// is a function of the one ratio g_q = l2 / den_q in (0, 1]:
 //     tt_q = 1 - g_q           =>  m_q = c - (c - m_bar) g_q                       (one fma per dimension)
 //     u_q = l2 (1 - g_q)       =>  the members carry v = l2 + u:  v_q = 2 l2 - l2 g_q,  W den_q = Ws d2_q + V  (no l2 + d2 add)
 //     den_q^(-D/2) = (g_q / l2)^(D/2),  -|c - m_bar|^2 / (2 den_q) = A g_q  with  A = -|c - m_bar|^2 / (2 l2)
 //     weight_q = Wm g_q^(D/2) exp(A g_q + lnT'[prev][q]),  lnT' = ln T - D/2 ln l2   (table built per workgroup: no T multiply, no gf)
-// The shared reciprocal R = 1 / (Ws Dq0 Dq1) stays: 1 / W = R Dq0 Dq1 and g_q = (R Ws^2 l2) Dq[1 - q].  61 fp64 operations for D = 2
-// against 73 of the general form.  The exponential's argument may be POSITIVE here (up to D/2 ln(1 / l2) = 41.4 at l2 = 1e-12, D = 3): the
-// bit extraction of xt_f2_exp_bits holds for either sign (two's complement of n in the mantissa field: j = n mod 1024, e = floor(n / 1024)
-// for |n| < 2^41; the magic-number rounding and the two-part reduction do not depend on the sign either), so xt_exp_tab_x2 is used as it
-// is, with its clamp of each argument from below.  (Clamping the shared factor A once instead is NOT equivalent: A is the squared jump in
-// units of l2, not of den - at l2 = 1e-10 an everyday displacement of 0.05 gives A = -1.3e7 while A g_q is of order -1.)
-// Lazy re-normalisation range: a child's mantissa is Wm g^(D/2) tj p with g = l2 / den in [1e-16, 1] (well-scaled bounds: l2 >= 1e-12,
-// den <= 1e4) and tj p in [1, 2): three un-normalised steps (merges double) stay within [1e-72, 64]; the products of a step are then
-// W^3 den^2 >= 1e-240 and R Ws^2 l2 <= 1e264 * 1e4 - the transition weight and l2^(-D/2) live in the integer exponent.
+// The shared reciprocal R = 1 / (Ws Dq0 Dq1) stays: 1 / W = R Dq0 Dq1 and g_q = (R Ws^2 l2) Dq[1 - q].
+// A member's weight is y exp(lx) (s.z = y, a lazily normalised double; lx, a double next to the lane state; s.e is not used): the child's exponential is never
+// taken - lx_q = A g_q + lnT'[prev][q] + base, y_q = Wm g_q^(D/2).  The merge of the NEXT step needs only the ratio of its two members,
+// ONE exponential E = exp(-|lx1 - lx0|) (xt_exp_tab_x1 with its clamp: E = 0 beyond 1.1e7, where the magic-number reduction would leave its
+// range) that scales the member with the smaller lx; base = max(lx0, lx1) is exact.  The absolute magnitude is only needed at the read-out
+// of the last position.  Against the form that exponentiated both children (16 fp64 + 2 table reads for the pair, 6 multiplies, 2 ldexp and
+// the integer exponent bookkeeping) the merge grows by the one exponential and two selects.
+// Lazy re-normalisation (every XT_F2_RENORM-th phase): Wm = frexp_mant(Ws), base += ln2 frexp_exp(Ws).  Range of the lazy mantissa:
+// y = Wm g^(D/2) with g = l2 / den in [1e-16, 1] (well-scaled bounds: l2 >= 1e-12, den <= 1e4) and a merge at most doubles the sum
+// (E <= 1): three un-normalised steps stay within [1e-72, 8]; the products of a step are then W^3 den^2 >= 1e-240 and
+// R Ws^2 l2 <= 1e264 * 1e4 - the transition weight and l2^(-D/2) live in lx.
+// Re-centring (phase XT_R2_RC_H, once per F - 1 steps): lx is rounded at ulp(|lx|), so it must not grow with the accumulated
+// log-likelihood.  The lanes of a track take the maximum of their truncated bases through an integer atomic max on the track's LDS cell
+// (LDS and cx.wave_sync() only): sh, an integer common to the track.  base -= sh (exact, or one rounding at the ulp of the small
+// difference) and the lane's LDS accumulator += sh (integers: exact); the read-out adds the accumulator to the track's log-likelihood.
+// The reference has to be the LARGEST base, not that of a fixed lane: a fixed lane's sequence may be hopeless (a still state on a moving
+// track is at -600 per step), and shifting by its base leaves |lx| in the thousands on the lanes that matter (measured: 1e-12 on
+// 33-position tracks at l2 = 1e-10).  In a re-normalisation phase y is in [0.5, 1), so the largest base is the dominant group's
+// log-weight to within ln 2, and the lanes that matter end within a few nats of 0; lanes far below are negligible at the read-out.
+// No execution mask and no branch: the step stays one basic block.  Between two re-centrings |lx| grows by at most F - 1 steps' worth
+// of log-weight (a few nats per step on ordinary data; at small l2 the lazy mantissa takes D/2 ln(den / l2) per step out of it until the next
+// re-normalisation: |lx| < 150 at l2 = 1e-12, D = 3, ulp 2.8e-14).
+#ifndef XT_R2_RC_H
+#define XT_R2_RC_H 0  // re-centring phase: a re-normalisation phase
+#endif
+#define XT_R2_RC_NONE (-2147483647 - 1)
 template <int F, int D, int H, bool FIRST = false, class Ctx>
-XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, int tab, const double* c)
+XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2], int tab, const double* c)
 {
     constexpr int NGB = F - 1;
     constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
@@ -335,18 +360,40 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, int tab, const
     }
     const double l2 = xt_at<double>(lds, 0), nh = xt_at<double>(lds, XT_R2_GC_OFF), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
 
-    // ---- merge (members carry v = l2 + u)
-    const int e0 = s.e[0], e1 = s.e[1];
-    const int emax = e0 > e1 ? e0 : e1;
-    const double w0 = FIRST ? 1.0 : xt_ldexp(s.z[0], e0 - emax), w1 = FIRST ? 0.0 : xt_ldexp(s.z[1], e1 - emax);
+    // ---- merge (members carry v = l2 + u): the member with the smaller lx is scaled by exp(-|lx1 - lx0|)
+    double w0 = 1.0, w1 = 0.0, base = lx[0];
+    if (!FIRST) {
+        const double dl = lx[1] - lx[0];
+        double p;
+        int j, n;
+        xt_exp_tab_x1(-fabs(dl), p, j, n);
+        const double E = xt_ldexp(xt_at<double>(lds, XT_F2_EXPB_OFF + j * 8) * p, n);  // n <= 0
+        const bool up = dl > 0.0;
+        w0 = s.z[0] * (up ? E : 1.0);
+        w1 = s.z[1] * (up ? 1.0 : E);
+        base = up ? lx[1] : lx[0];
+    }
     const double Ws = FIRST ? 1.0 : w0 + w1;
     double M[D];
     XT_UNROLL
     for (int d = 0; d < D; ++d) M[d] = FIRST ? s.m[0][d] : xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
     const double V = FIRST ? s.u[0][0] : xt_fma(w1, s.u[1][0], w0 * s.u[0][0]);
-    constexpr bool RN = (H % XT_F2_RENORM) == 0;
+    constexpr bool RN = !FIRST && (H % XT_F2_RENORM) == 0;
     const double Wm = FIRST ? s.z[0] : (RN ? xt_frexp_mant(Ws) : Ws);
-    const int We = FIRST ? e0 : (RN ? emax + xt_frexp_exp(Ws) : emax);
+    if (RN) base = xt_fma((double)xt_frexp_exp(Ws), XT_LN2, base);
+    if (!FIRST && H == XT_R2_RC_H) {
+        // re-centring: the integer shift is the largest (truncated) base among the track's lanes - an atomic max on the track's LDS cell,
+        // which every lane of the track reset one phase later in the previous pass (or at position 0)
+        const int tid = xt_opaque(cx.tid());
+        const int rc0 = xt_r2_rc0(D, 0, XtR2Geom<F>::TPW);  // g-form launches stage no per-peak errors (KS = 0)
+        const int cell = rc0 + (tid & ~xt_r2_gmask(F)) * 8;
+        cx.atomic_max_i32(&xt_at<int>(lds, cell), (int)fmin(fmax(base, -1e9), 1e9));  // a NaN base (poisoned track) counts as -1e9
+        cx.wave_sync();
+        const int sh = xt_at<int>(lds, cell);
+        base -= (double)sh;
+        xt_at<unsigned int>(lds, rc0 + XT_R2_RC_ARR + tid * 8) += (unsigned int)sh;  // read back as int; wraps only on a poisoned track (-1e9 per pass)
+    }
+    if (!FIRST && H == (XT_R2_RC_H + 1) % NGB) xt_at<int>(lds, xt_r2_rc0(D, 0, XtR2Geom<F>::TPW) + (xt_opaque(cx.tid()) & ~xt_r2_gmask(F)) * 8) = XT_R2_RC_NONE;
 
     // ---- the shared reciprocal, g_q
     const double Dq0 = xt_fma(Ws, TD2[0], V), Dq1 = xt_fma(Ws, TD2[1], V);
@@ -362,30 +409,24 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, int tab, const
         dsq = xt_fma(dn[d], dn[d], dsq);
     }
     const double A = dsq * nh;
-    double p[2];
-    int j[2], n[2];
-    xt_exp_tab_x2(xt_fma(A, g[0], LT[0]), xt_fma(A, g[1], LT[1]), p[0], p[1], j[0], j[1], n[0], n[1]);
-    double nz[2], nm[2][D], nv[2];
-    int ne[2];
+    double ny[2], nl[2], nm[2][D], nv[2];
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
-        const int en = We + n[q];
-        const double tj = xt_at<double>(lds, XT_F2_EXPB_OFF + j[q] * 8);
-        nz[q] = (Wm * xt_pow_half<D>(g[q])) * (tj * p[q]);
-        ne[q] = en > XT_EMIN ? en : XT_EMIN;
+        ny[q] = Wm * xt_pow_half<D>(g[q]);
+        nl[q] = xt_fma(A, g[q], LT[q]) + base;
         XT_UNROLL
         for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(-dn[d], g[q], c[d]);
         nv[q] = xt_fma(-l2, g[q], l22);
     }
-    cx.template pair_exchange<XB>(nz[0], nz[1]);
-    cx.template pair_exchange_i32<XB>(ne[0], ne[1]);
+    cx.template pair_exchange<XB>(ny[0], ny[1]);
+    cx.template pair_exchange<XB>(nl[0], nl[1]);
     XT_UNROLL
     for (int d = 0; d < D; ++d) cx.template pair_exchange<XB>(nm[0][d], nm[1][d]);
     cx.template pair_exchange<XB>(nv[0], nv[1]);
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
-        s.z[q] = nz[q];
-        s.e[q] = ne[q];
+        s.z[q] = ny[q];
+        lx[q] = nl[q];
         XT_UNROLL
         for (int d = 0; d < D; ++d) s.m[q][d] = nm[q][d];
         s.u[q][0] = nv[q];
@@ -495,7 +536,9 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     constexpr int NGB = Gm::NGB, TPW = Gm::TPW;
     constexpr int GMASK = xt_r2_gmask(F);
     const int lane = cx.lane();
-    const int wib = cx.wave_in_block();
+    // likelihood only: the wave index as a scalar (batch, track and LDS base addresses then stay out of the vector registers: the kernel sits at
+    // the 128-VGPR limit of four waves per SIMD)
+    const int wib = NP == 0 ? cx.uniform(cx.wave_in_block()) : cx.wave_in_block();
     const int nwb = cx.waves_per_block();
     const int L = b.L;
     const int KS = a.locerr_mode ? a.KS : 0;
@@ -544,11 +587,19 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     double* sig = pos + TPW * XT_F2_CHUNK * D;                                           // [TPW][CHUNK][KS]
     // per (wave, track slot): NP == 0 {mantissa, exponent, count} of the running likelihood product; NP > 0 {sum LL, sum dLL_p}
     double* accp = (double*)(lds + xt_r2_acc0(NPT, D, KS, TPW)) + (wib * 8 + ts) * (NPT + 3);
+    // NP == 0 reaches them by a byte address formed where it is used, as the re-centring cells below: nothing more is kept in registers
+    // across the step loop
+    auto accb = [&]() XT_INL { return xt_r2_acc0(0, D, KS, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 24; };
+    // likelihood only: this lane's accumulated re-centring shift (xt_r2_step_g), and per (wave, slot) the sum over the finished tracks
+    auto rcacc = [&]() XT_INL { return xt_r2_rc0(D, KS, TPW) + XT_R2_RC_ARR + xt_opaque(cx.tid()) * 8; };
+    auto rcsum = [&]() XT_INL { return xt_r2_rc0(D, KS, TPW) + 2 * XT_R2_RC_ARR + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 8; };
     if (leader) {
         if (NP == 0) {
-            accp[0] = 1.0;
-            accp[1] = 0.0;
-            accp[2] = 0.0;
+            const int ab = accb();
+            xt_at<double>(lds, ab) = 1.0;
+            xt_at<double>(lds, ab + 8) = 0.0;
+            xt_at<double>(lds, ab + 16) = 0.0;
+            xt_at<double>(lds, rcsum()) = 0.0;
         } else {
             for (int i = 0; i < NPT + 1; ++i) accp[i] = 0.0;
         }
@@ -608,6 +659,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
 
         XtR2Lane<D, K, NP> s;
+        double lx[2] = {0.0, 0.0};  // log part of the members' weights (xt_r2_step_g); the read-out adds it to the exponential's argument: zero unless log-carried steps ran
 #define XT_R2_PHASE(H, ZF_, LAZY_)                                                                     \
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
@@ -620,7 +672,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
         getpos(t, c, l2);                                                                              \
-        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, XT_R2_TABSEL, c);                        \
+        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lx, XT_R2_TABSEL, c);                        \
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
@@ -681,6 +733,10 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         int fe = XT_EMIN;
         int t = 1;
         if (lane < 8) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + lane) * 4) = 0;
+        if (NP == 0) {
+            xt_at<int>(lds, rcacc()) = 0;
+            xt_at<int>(lds, rcacc() - XT_R2_RC_ARR) = XT_R2_RC_NONE;  // the lane's own cell: the track's leader resets the one in use
+        }
         for (int p0 = 0; p0 < L; p0 += XT_F2_CHUNK) {
             stage(p0);
             if (p0 == 0) {
@@ -724,9 +780,11 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                             getpos(F - 1, c, l2);
                             bool first_done = false;
                             if constexpr (K == 1) {
-                                if (gform) {  // from here on the members carry v = l2 + u (until the read-out of the last position)
+                                if (gform) {  // from here on the members carry v = l2 + u and weights y exp(lx) (until the read-out of the last position)
                                     s.u[0][0] += l2[0];
-                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
+                                    lx[0] = (double)s.e[0] * XT_LN2;
+                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lx, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
+                                    s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lx now
                                     first_done = true;
                                 }
                             }
@@ -773,6 +831,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         const double r = xt_rcp(d2 + s.u[Q][0] + l2l[0]);
                         rr[Q * 2 + q][0] = r;
                         x[q] = -0.5 * dsqQ[Q] * r;
+                        if constexpr (NP == 0) x[q] += lx[Q];  // log-carried weights (xt_r2_step_g): y exp(lx), e = 0
                         gf[q] = xt_pow_half<D>(r);
                     } else {
                         double xx = 0.0, gg = 1.0;
@@ -854,14 +913,19 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         const bool poisoned = xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + ts) * 4) != 0;
         if (poisoned) sum = NAN;  // NaN input -> NaN likelihood, as in the reference
         if (NP == 0) {
-            if (act && leader) {
-                if (b.ll_out) b.ll_out[trk] = log(sum) + (double)fe * XT_LN2 + b.ll_const;
-                const double pm = accp[0] * xt_frexp_mant(sum);
-                double acce = accp[1] + (double)(fe + xt_frexp_exp(sum) + xt_frexp_exp(pm));
+            const int lz = xt_opaque(cx.lane());
+            const int64_t trk = batch * TPW + xt_r2_slot<F>(lz);  // formed again: not held across the step loop
+            if (trk < b.N && (lz & GMASK) == 0) {
+                const double rcs = (double)xt_at<int>(lds, rcacc());  // 0 unless log-carried steps ran
+                if (b.ll_out) b.ll_out[trk] = log(sum) + (double)fe * XT_LN2 + b.ll_const + rcs;
+                xt_at<double>(lds, rcsum()) += rcs;
+                const int ab = accb();
+                const double pm = xt_at<double>(lds, ab) * xt_frexp_mant(sum);
+                double acce = xt_at<double>(lds, ab + 8) + (double)(fe + xt_frexp_exp(sum) + xt_frexp_exp(pm));
                 if (sum == 0.0) acce = -INFINITY;
-                accp[0] = xt_frexp_mant(pm);
-                accp[1] = acce;
-                accp[2] += 1.0;
+                xt_at<double>(lds, ab) = xt_frexp_mant(pm);
+                xt_at<double>(lds, ab + 8) = acce;
+                xt_at<double>(lds, ab + 16) += 1.0;
             }
         } else {
             const double rs = 1.0 / sum;
@@ -895,7 +959,10 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     // ---- per-slot sums -> block partials (fixed order)
     cx.sync();
     if (NP == 0) {
-        if (leader) smem[wib * TPW + ts] = accp[2] > 0.0 ? log(accp[0]) + accp[1] * XT_LN2 + accp[2] * b.ll_const : 0.0;
+        if (leader) {
+            const double* ac = &xt_at<double>(lds, accb());
+            smem[wib * TPW + ts] = ac[2] > 0.0 ? log(ac[0]) + ac[1] * XT_LN2 + ac[2] * b.ll_const + xt_at<double>(lds, rcsum()) : 0.0;
+        }
         cx.sync();
         if (cx.tid() == 0) {
             double sacc = 0.0;

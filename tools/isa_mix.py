@@ -7,7 +7,7 @@ reads the result (profiles/isa_mix.json) for its fp64-issue figures instead of h
 Method: the likelihood-only register-resident kernel (csrc/xt_reg2.h) unrolls its step loop over the F - 1 exchange phases in three
 variants; the basic blocks with >= 50 fp64 vector instructions and the table reads are the steps.  The steady-state ones (well-scaled model:
 zero-free, lazily re-normalised) are the 2 (F - 1) with the fewest instructions among the blocks of the innermost loops (the loop depth the
-compiler notes at every block label); the step outside them is the merge-free first step (position F - 1), and the F - 2 blocks with one
+compiler notes at every block label); the first step-sized block outside them is the merge-free first step (position F - 1; the read-out of the last position follows it), and the F - 2 blocks with one
 v_rcp_f64 right before it are the warm-up chain (positions 1 .. F - 2, one block each).  Counts are per wave-step (one wavefront = 64 / 2^(F-1) tracks,
 one position)."""
 import json, os, re, subprocess, sys, tempfile
@@ -62,7 +62,7 @@ for line in open(os.path.join(tmp, asm)):
 steps = sorted([b for b in blocks if b["f64"] >= 50 and b["lds"] >= 4], key=lambda b: b["f64"] + b["valu32"])
 maxd = max(b["depth"] for b in steps)
 ss = [b for b in steps if b["depth"] == maxd][:2 * (F - 1)]  # the step loop is inlined twice (before / after the stay-in-FOV factor sets in): both copies of the F - 1 phases
-first = [b for b in steps if b["depth"] < maxd]
+first = sorted([b for b in steps if b["depth"] < maxd], key=blocks.index)[:1]  # the read-out of the last position, a block of this size too, comes after it
 at = blocks.index(first[0]) if len(first) == 1 else 0
 chain = [b for b in blocks[:at] if b["depth"] == maxd - 1 and 20 <= b["f64"] < 50 and b["trans"] == 1][-(F - 2):] if at else []
 n = float(len(ss))
