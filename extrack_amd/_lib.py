@@ -16,7 +16,7 @@ EXPORTS = [
     "extrack_upload_bucket", "extrack_attach_bucket", "extrack_set_bucket_dt", "extrack_clear_buckets", "extrack_bucket_count",
     "extrack_loglik", "extrack_loglik_async", "extrack_predict", "extrack_last_kernel_ms",
     "extrack_last_launch_info", "extrack_p_stay_table", "extrack_loglik_th", "extrack_loglik_th_async", "extrack_th_plan_step",
-    "extrack_predict_th", "extrack_loglik_grad", "extrack_loglik_grad_async", "extrack_last_grad_ms", "extrack_segment_len_hist", "extrack_refine_positions",
+    "extrack_predict_th", "extrack_loglik_grad", "extrack_loglik_grad_async", "extrack_loglik_scores", "extrack_loglik_scores_async", "extrack_last_grad_ms", "extrack_segment_len_hist", "extrack_refine_positions",
     "extrack_refine_pos_pdf",
     "extrack_sequence_columns", "extrack_sequence_matrix", "extrack_loglik_th_grad", "extrack_loglik_th_grad_async", "extrack_th_freeze_plan", "extrack_sequence_matrix_th",
     "extrack_multi_create", "extrack_multi_destroy", "extrack_multi_last_error", "extrack_multi_device_count", "extrack_multi_uses_rccl",
@@ -111,6 +111,8 @@ def load():
     lib.extrack_th_plan_step.argtypes = [vp, i32, i64, i32, C.POINTER(i32), C.POINTER(i32), vp, vp, i32]
     lib.extrack_loglik_grad.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), _dp, vp]
     lib.extrack_loglik_grad_async.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), vp]
+    lib.extrack_loglik_scores.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), _dp, vp, vp, vp]
+    lib.extrack_loglik_scores_async.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), vp]
     lib.extrack_segment_len_hist.argtypes = [vp, C.POINTER(ExtrackModel), i32, i32, vp]
     lib.extrack_refine_positions.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, vp]
     lib.extrack_refine_pos_pdf.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, i64, vp, vp, vp]
@@ -309,6 +311,23 @@ class Context:
         {sum LL, gradient} in stream order (the multi-GPU objective all-reduces it there)."""
         n, arr, keep = self._pack_tangents(model, tangents)
         self._check(self._lib.extrack_loglik_grad_async(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
+        return n
+
+    def loglik_scores(self, model, tangents, scores=False):
+        """(sum LL, gradient [n], opg [n, n]) and, with ``scores``, the per-track scores [n_tracks, n] (rows: the buckets in upload order,
+        as ``loglik(per_track=True)``) for the model directions ``tangents``: extrack_loglik_scores, forward-mode kernels only."""
+        n, arr, keep = self._pack_tangents(model, tangents)
+        tot = C.c_double(0.0)
+        g, B = np.zeros(max(n, 1)), np.zeros((max(n, 1), max(n, 1)))
+        sc = np.empty((self.n_tracks(), n)) if scores else None
+        self._check(self._lib.extrack_loglik_scores(self._h, C.byref(model.c), n, arr, C.byref(tot), g.ctypes.data_as(C.c_void_p),
+                                                    B.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p) if scores else None))
+        return (tot.value, g, B, sc) if scores else (tot.value, g, B)
+
+    def loglik_scores_async(self, model, tangents, d_out_ptr):
+        """Enqueues the evaluation; the DEVICE buffer ``d_out_ptr`` (1 + n + n * n doubles) receives {sum LL, gradient, opg} in stream order."""
+        n, arr, keep = self._pack_tangents(model, tangents)
+        self._check(self._lib.extrack_loglik_scores_async(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
         return n
 
     def sequence_matrix_th(self, model, bucket_id, threshold=0.2, max_nb_states=120):

@@ -7,6 +7,7 @@
 #include "xt_reg2.h"
 #include "xt_gradr.h"
 #include "xt_rev.h"
+#include "xt_opg.h"
 
 // Waves per SIMD the register allocator is asked to allow.  Measured on C2 (1e6 x 30, 7 directions, PJ = 4): 2 -> 63 ms,
 // 3 -> 53 ms (168 VGPRs, 108 B of scratch per lane), 4 -> 60 ms (128 VGPRs, 272 B of scratch).  Three members per group (C3, 13 directions): 3 waves (232 B of
@@ -138,7 +139,11 @@ static int xt_grad_reserve(extrack_ctx* ctx, double** buf, size_t* cap, size_t n
 
 // Enqueues the kernels of one likelihood + gradient evaluation on the context's stream; d_out (device, 1 + n_dir doubles) receives
 // {sum LL, d sum LL / d theta_i}.  Nothing waits for the device: passes and launch groups accumulate in stream order.
-static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out)
+// d_scores (device, [sum N][n_dir], or nullptr): a scores evaluation - the forward-mode kernels also store every track's dLL_n/dtheta, rows
+// in bucket-id order, columns in launch order (cols->idx[c] = the caller's direction of column c); the reverse-mode kernels are bypassed
+// (their adjoints are accumulated across tracks) and d_opg (device, [n_dir][n_dir], or nullptr) receives sum_n s_n s_n^T.
+static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out,
+                           double* d_scores = nullptr, XtOpgCols* cols = nullptr, double* d_opg = nullptr)
 {
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
@@ -190,6 +195,12 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
         groups.back().push_back(b);
     }
     if (order.size() > (size_t)XT_DESC_CAP / 2) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "too many buckets");
+    if (d_scores && groups.size() > 1)
+        return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "per-track scores: buckets of different layouts or more than 64 track lengths");
+    int64_t n_total = 0;
+    for (auto& b : ctx->buckets) n_total += b.N;
+    if (d_scores)
+        for (int i = 0; i < XT_OPG_MAXDIR; ++i) cols->idx[i] = i;
 
     // more than one launch group (more than XT_MAX_BUCKETS track lengths, or buckets of different layouts): the groups after the first write
     // {sum LL, gradient} to a scratch row that is added to d_out in stream order
@@ -235,6 +246,11 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             d.L = b->L;
             d.isBL = (b->L != m->max_len) ? 1 : 0;  // tracking.py:1037-1040
             d.ll_const = -(double)(b->L - 1) * D * 0.5 * XT_LOG2PI;
+            if (d_scores) {  // rows of the buckets uploaded before this one come first (the order of extrack_loglik's per_track)
+                int64_t row0 = 0;
+                for (const XtBucket* o = ctx->buckets.data(); o != b; ++o) row0 += o->N;
+                d.scores_out = d_scores + row0 * n_dir;
+            }
             descs.push_back(d);
         }
         ctx->desc_shadow.clear();  // this path writes the device table itself: the likelihood launcher's shadow of it no longer holds
@@ -258,7 +274,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             for (auto& d : descs) Lmax0 = std::max(Lmax0, (int)d.L);
             const size_t slot_doubles = (size_t)tpb * std::max(Lmax0 - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
             const size_t max_blocks = (ctx->rev_log_mb << 20) / (slot_doubles * sizeof(double));
-            const bool use_rev = kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
+            const bool use_rev = !d_scores && kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
                                  (ctx->grad_rev == 2 || (ctx->grad_rev == 1 && ctx->grad_reg2 == 1 && !r2));
             if (use_rev) {
                 if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -338,6 +354,8 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                 return v >= 1 && v <= 8 ? v : 8;
             }();
             const int npass = (NF + r2_maxnp - 1) / r2_maxnp, per = (NF + npass - 1) / npass;
+            if (d_scores)
+                for (int i = 0; i < n_dir; ++i) cols->idx[i] = i < NF ? full[i] : uni[i - NF];
             double lo = INFINITY, hi = -INFINITY;
             for (int k = 0; k < m->locerr_dims && k < 3; ++k) {
                 lo = std::min(lo, m->locerr[k] * m->locerr[k]);
@@ -382,6 +400,9 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                 ga.TB = TB;
                 ga.NU = NU;
                 ga.udblob = ctx->d_dblob2 + (size_t)NF * TB;
+                ga.score_ld = n_dir;
+                ga.score_col0 = p0;
+                ga.score_ucol0 = NF;
                 void* kargs[2] = {(void*)&a, (void*)&ga};
                 XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
                 XtGradDst dst = xt_grad_dst_identity(0);  // column 1 + i of this launch -> the caller's direction index
@@ -451,6 +472,8 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                     ga.gpartials = ctx->d_gpartials + poff;
                     ga.NP = NP;
                     ga.TB = TB;
+                    ga.score_ld = n_dir;
+                    ga.score_col0 = p0;
                     void* kargs[2] = {(void*)&a, (void*)&ga};
                     XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
                     hipLaunchKernelGGL(xt_grad_reduce, dim3(NP + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, grid, NP + 1,
@@ -521,6 +544,8 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             l.ga.TB = TB;
             l.ga.tan_lds = tan_lds ? 1 : 0;
             l.ga.PJ = PJ;
+            l.ga.score_ld = n_dir;
+            l.ga.score_col0 = p0;
             if (!xt_grad_dispatch(c.G, D, K, l)) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
             if (l.herr != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("gradient kernel launch: ") + hipGetErrorString(l.herr));
             if (NP > 16) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "more than 16 directions per pass");
@@ -537,6 +562,11 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
         }
         doff += g.size();
         group_done();
+    }
+    if (d_scores && d_opg) {
+        int rc2 = xt_grad_reserve(ctx, &ctx->d_opgpart, &ctx->opgpart_cap, (size_t)xt_opg_tiles(n_total) * xt_opg_pairs(n_dir));
+        if (rc2) return rc2;
+        xt_opg_launch(ctx->stream, d_scores, n_total, n_dir, ctx->d_opgpart, d_opg, *cols);
     }
     XT_HIP(ctx, hipGetLastError());
     XT_HIP(ctx, hipEventRecord(ctx->evg1, ctx->stream));
@@ -565,6 +595,61 @@ extern "C" int extrack_loglik_grad(extrack_ctx* ctx, const extrack_model* m, int
     XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *total_ll = host[0];
     for (int i = 0; i < n_dir; ++i) grad[i] = host[1 + i];
+    return EXTRACK_OK;
+}
+
+// Validation + the device score matrix [sum N][n_dir] of a scores evaluation (kept with the context)
+static int xt_scores_prepare(extrack_ctx* ctx, int32_t n_dir, const extrack_model_tangent* tangents)
+{
+    if (!ctx || n_dir < 1 || !tangents) return xt_fail(ctx, EXTRACK_E_INVALID, "per-track scores need at least one direction");
+    if (n_dir > XT_OPG_MAXDIR) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "per-track scores: more than 32 directions");
+    int64_t n_total = 0;
+    for (auto& b : ctx->buckets) n_total += b.N;
+    if (n_total < 1) return xt_fail(ctx, EXTRACK_E_INVALID, "no track uploaded");
+    return xt_grad_reserve(ctx, &ctx->d_scores, &ctx->scores_cap, (size_t)n_total * n_dir);
+}
+
+extern "C" int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                           double* d_out)
+{
+    if (!ctx || !d_out) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
+    int rc = xt_scores_prepare(ctx, n_dir, tangents);
+    if (rc) return rc;
+    XtOpgCols cols;
+    return xt_grad_enqueue(ctx, m, n_dir, tangents, d_out, ctx->d_scores, &cols, d_out + 1 + n_dir);
+}
+
+extern "C" int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                     double* total_ll, double* grad, double* opg, double* scores)
+{
+    if (!ctx || !total_ll) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
+    int rc = xt_scores_prepare(ctx, n_dir, tangents);
+    if (rc) return rc;
+    const size_t nd = (size_t)n_dir;
+    if ((rc = xt_grad_reserve(ctx, &ctx->d_gout, &ctx->gout_cap, 1 + nd + nd * nd))) return rc;
+    XtOpgCols cols;
+    if ((rc = xt_grad_enqueue(ctx, m, n_dir, tangents, ctx->d_gout, ctx->d_scores, &cols, opg ? ctx->d_gout + 1 + nd : nullptr))) return rc;
+    std::vector<double> host(1 + nd + nd * nd);
+    XT_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gout, (opg ? host.size() : 1 + nd) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (scores) {
+        size_t n_total = 0;
+        for (auto& b : ctx->buckets) n_total += (size_t)b.N;
+        bool launch_order = true;
+        for (int i = 0; i < n_dir; ++i) launch_order = launch_order && cols.idx[i] == i;
+        std::vector<double> tmp(launch_order ? 0 : n_total * nd);
+        XT_HIP(ctx, hipMemcpyAsync(launch_order ? scores : tmp.data(), ctx->d_scores, n_total * nd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (!launch_order)  // columns from launch order to the caller's order
+            for (size_t r = 0; r < n_total; ++r)
+                for (int i = 0; i < n_dir; ++i) scores[r * nd + cols.idx[i]] = tmp[r * nd + i];
+    } else {
+        XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    *total_ll = host[0];
+    if (grad)
+        for (int i = 0; i < n_dir; ++i) grad[i] = host[1 + i];
+    if (opg)
+        for (size_t i = 0; i < nd * nd; ++i) opg[i] = host[1 + nd + i];
     return EXTRACK_OK;
 }
 

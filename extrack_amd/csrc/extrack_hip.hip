@@ -280,6 +280,8 @@ extern "C" void extrack_destroy(extrack_ctx* ctx)
     if (ctx->ev_dblob) (void)hipEventDestroy(ctx->ev_dblob);
     if (ctx->d_gout) (void)hipFree(ctx->d_gout);
     if (ctx->d_gtmp) (void)hipFree(ctx->d_gtmp);
+    if (ctx->d_scores) (void)hipFree(ctx->d_scores);
+    if (ctx->d_opgpart) (void)hipFree(ctx->d_opgpart);
     if (ctx->d_revlog) (void)hipFree(ctx->d_revlog);
     if (ctx->d_revadj) (void)hipFree(ctx->d_revadj);
     for (int i = 0; i < extrack_ctx::RF_SLOTS; ++i)

@@ -39,6 +39,9 @@ struct XtGradArgs {
     int32_t PJ;            // threads per group: thread (g, j) carries the directions j, j + PJ, ... (power of two, adjacent lanes)
     int32_t NU;            // register-resident 2-state kernels (xt_reg2.h): "uniform" directions handled at the last position only
     const double* udblob;  // [NU][TB] their tangent tables
+    // per-track scores (XtBucketDesc::scores_out set): direction p of this pass goes to column score_col0 + p of a row of score_ld doubles,
+    // uniform direction u to column score_ucol0 + u
+    int32_t score_ld = 0, score_col0 = 0, score_ucol0 = 0;
 };
 // Tangent table block of one direction (TB doubles):
 //   [0..2] d l2 (global localisation error),  [3] d slope,  [4] d offset,  [8 + s] d log Fs[s]
@@ -492,7 +495,9 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                     if (b.ll_out) b.ll_out[trk] = ll;
                     bacc[0] += ll;
                 } else {
-                    bacc[col] += poisoned ? NAN : csum[col] / sw;
+                    const double sc = poisoned ? NAN : csum[col] / sw;
+                    if (b.scores_out) b.scores_out[trk * ga.score_ld + ga.score_col0 + col - 1] = sc;
+                    bacc[col] += sc;
                 }
             }
         }

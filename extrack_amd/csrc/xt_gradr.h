@@ -485,7 +485,9 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                     if (b.ll_out) b.ll_out[trk] = ll;
                     bacc[0] += ll;
                 } else {
-                    bacc[col] += poisoned ? NAN : csum[col] / sw;
+                    const double sc = poisoned ? NAN : csum[col] / sw;
+                    if (b.scores_out) b.scores_out[trk * ga.score_ld + ga.score_col0 + col - 1] = sc;
+                    bacc[col] += sc;
                 }
             }
         }

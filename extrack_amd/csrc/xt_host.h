@@ -290,6 +290,10 @@ struct extrack_ctx {
     size_t gout_cap = 0;
     double* d_gtmp = nullptr;       // ... of the launch groups after the first (added to the result in stream order)
     size_t gtmp_cap = 0;
+    double* d_scores = nullptr;     // scores evaluation (extrack_loglik_scores): per-track dLL_n/dtheta [sum N][n_dir]
+    size_t scores_cap = 0;
+    double* d_opgpart = nullptr;    // ... per-tile partial sums of its outer products (xt_opg.h)
+    size_t opgpart_cap = 0;
     double* d_partials = nullptr;
     size_t partials_cap = 0;
     static constexpr int RF_SLOTS = 10;   // position refinement: grow-only device buffers kept between calls (extrack_hip.hip: XT_RF_*)

@@ -45,6 +45,7 @@ struct XtBucketDesc {
     int32_t L, isBL;
     double ll_const;       // -(L-1)*D/2*log(2*pi)
     double* seq_out = nullptr;  // [N][E][G] log-weight of every (stored sequence, new digits) at the last position, or nullptr (xt_seqmat.h)
+    double* scores_out = nullptr;  // forward-mode gradient kernels: row 0 of this bucket in the per-track score matrix [N][XtGradArgs::score_ld], or nullptr
 };
 
 struct XtKernelArgs {

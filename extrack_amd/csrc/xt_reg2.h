@@ -941,6 +941,11 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 accp[0] += ll;
                 XT_UNROLL
                 for (int pp = 0; pp < NP; ++pp) accp[1 + pp] += gsum[pp] * rs;
+                double* const srow = b.scores_out ? b.scores_out + trk * ga.score_ld : nullptr;  // this track's row of the score matrix
+                if (srow) {
+                    XT_UNROLL
+                    for (int pp = 0; pp < NP; ++pp) srow[ga.score_col0 + pp] = gsum[pp] * rs;
+                }
                 // uniform directions: d log of the initial fraction + one constant per step (without / with the stay-in-FOV factor)
                 const int nsteps = L - 2 > 0 ? L - 2 : 0;
                 const int n1 = nsteps >= stay_from ? nsteps - stay_from + 1 : 0, n0 = nsteps - n1;
@@ -950,6 +955,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         const int tb = XT_R2_TAN0 + (NP + u) * XT_R2_TB * 8;
                         const double rzu = xt_at<double>(lds, tb + 8 * 8) + n0 * xt_at<double>(lds, tb + XT_R2_TAB0) + n1 * xt_at<double>(lds, tb + XT_R2_TAB0 + 32);
                         accp[1 + NP + u] += usum[u] * rs + rzu;
+                        if (srow) srow[ga.score_ucol0 + u] = usum[u] * rs + rzu;
                     }
             }
         }

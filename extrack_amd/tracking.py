@@ -609,7 +609,7 @@ def _fit_threshold_frozen_plan(params, fargs, method, ts, max_rounds=6):
 # ------------------------------------------------------------------------------------------------------------
 def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame_len=6, verbose=1, workers=1, Matrix_type=1,
                   method="bfgs", steady_state=False, cell_dims=[1], input_LocErr=None, threshold=0.2, max_nb_states=120,
-                  device=None, comm=None, fusion=None, gradient=None):
+                  device=None, comm=None, fusion=None, gradient=None, uncertainties=None):
     """Fit the model parameters to a length-bucketed track dict (extrack/tracking.py:1299-1386).
 
     all_tracks: {str(len): ndarray[n_tracks, len, dims]}.  Returns the lmfit (or lmfit_compat) MinimizerResult:
@@ -618,8 +618,17 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     shard), ``fusion`` ("window" | "threshold" | None = process default, see the module docstring), ``gradient``
     ("analytic": the optimiser gets the exact gradient from the GPU, one evaluation per iteration; "fd": it differences the
     objective like the reference's; None: analytic where it exists (fixed-window kernel, gradient-based method, differentiable
-    constraint expressions) AND a timing probe on this dataset says it is the cheaper way to a gradient, else fd: ``_pick_gradient``)."""
+    constraint expressions) AND a timing probe on this dataset says it is the cheaper way to a gradient, else fd: ``_pick_gradient``),
+    ``uncertainties`` (None / False: point estimates only, as the reference; True or "opg" | "hessian" | "sandwich": after the fit the
+    covariance of the free parameters is estimated on the same device-resident tracks - ``extrack_amd.uncertainty`` - and written to
+    ``fit.covar``, ``fit.params[name].stderr`` / ``.correl``, ``fit.errorbars``, ``fit.uncertainty_method``, ``fit.uncertainty_message``;
+    fixed-window kernel with a scalar ``dt`` only)."""
+    from . import uncertainty
     fusion = "threshold" if _check_fusion(fusion) else "window"
+    unc_method = uncertainty.resolve_method(uncertainties)
+    if unc_method is not None and (fusion == "threshold" or isinstance(dt, (dict, list))):
+        raise NotImplementedError("uncertainties need per-track scores, which the fixed-window kernels with a scalar dt provide: "
+                                  "not built for fusion='threshold' or per-track time steps")
     device = _resolve_device(device, comm)
     if params is None:
         params = generate_params(nb_states=nb_states, LocErr_type=1, LocErr_bounds=[0.005, 0.1], D_max=3,
@@ -662,6 +671,9 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
                                                       fcn_grad=cum_Proba_Cs_grad)
         else:
             fit = minimize(cum_Proba_Cs, params, args=fargs, method=method, nan_policy="propagate")
+        if unc_method is not None:
+            uncertainty.attach(fit, uncertainty.parameter_uncertainties(ts, dt, fit.params, nb_states, nb_substeps, frame_len, cell_dims, None,
+                                                                        Matrix_type, device, unc_method, comm))
     finally:
         ts.close()
     # which way the optimiser got its gradient, and why (the fit's record; `ngev` > 0 says the same for the built-in driver)

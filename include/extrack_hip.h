@@ -38,6 +38,9 @@
  *       extrack_loglik AND its exact gradient in one pass.  It replaces the finite-difference loop that the reference's
  *       optimiser runs around cum_Proba_Cs (lmfit.minimize at extrack/tracking.py:1371: BFGS evaluates the objective
  *       nvar + 1 times per iteration to difference it numerically).
+ *   extrack_loglik_scores
+ *       the same evaluation keeping every track's own dLL_n/dtheta and their outer-product sum: what the parameter standard errors
+ *       of a fit are computed from (the reference returns point estimates only).
  *   extrack_loglik_th_grad
  *       extrack_loglik_th AND the exact gradient of that value at the evaluation's own merge plan - the objective v1.6.3's
  *       param_fitting hands to lmfit.minimize (extrack/tracking.py:1371 -> cum_Proba_Cs :991 -> P_Cs_inter_bound_stats_th :427-650);
@@ -205,6 +208,25 @@ int extrack_th_freeze_plan(extrack_ctx* ctx, int32_t on);
  * inputs (n * n_cols doubles cross the host); the likelihood path never forms it. */
 int extrack_sequence_matrix_th(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double threshold, int32_t max_nb_states,
                                double* lp, int64_t n_cols_cap, int64_t* n_cols_out);
+/* Per-track scores.  One evaluation as extrack_loglik_grad that also keeps every track's own derivative s_n = d LL_n / d theta (the
+ * forward-mode kernels hold it just before they sum over tracks) and, tracks being independent, reduces it on the device to the outer
+ * product of gradients opg[i][j] = sum_n s_ni s_nj (fp64, fixed summation order: bit-reproducible; exactly symmetric) - an estimate of
+ * the Fisher information whose inverse is the BHHH covariance of a fitted theta.  total_ll and grad (n_dir entries, or NULL) as
+ * extrack_loglik_grad; opg: host [n_dir * n_dir] row-major, or NULL (then the reduction is skipped); scores: host [sum N][n_dir], the
+ * buckets concatenated in id order as the per_track output of extrack_loglik, or NULL (the N x n_dir matrix then never leaves the
+ * device).  A track with a NaN position has a NaN row, and opg is then not finite.  Always the forward-mode kernels (csrc/xt_reg2.h,
+ * xt_gradr.h, xt_grad.h) - the reverse-mode kernels accumulate their adjoints across tracks and have no per-track score - so for 3 / 4
+ * states one call costs several extrack_loglik_grad calls: meant to be called once per fit, not once per iteration.  1 <= n_dir <= 32
+ * (n_dir == 0: EXTRACK_E_INVALID).  Restriction as extrack_loglik_grad: ONE launch group, EXTRACK_E_UNSUPPORTED otherwise.  The device
+ * score matrix (sum N * n_dir doubles) stays allocated with the context.  The first reduction stage sums tiles of EXTRACK_OPG_TILE
+ * tracks. */
+#define EXTRACK_OPG_TILE 1024
+int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                          double* total_ll, double* grad, double* opg, double* scores);
+/* The same, enqueued on the context's stream: d_out (DEVICE, 1 + n_dir + n_dir * n_dir doubles) receives {sum LL, gradient, opg
+ * row-major} in stream order - a multi-GPU caller all-reduces that buffer; the scores themselves are never gathered. */
+int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                                double* d_out);
 /* Device time (ms) of the gradient kernels of the last extrack_loglik_grad / extrack_loglik_th_grad (or _async) call (waits for them). */
 int extrack_last_grad_ms(extrack_ctx* ctx, float* ms);
 
