@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("EXTRACK_HIP_LIB", os.path.join(_HERE, "libextrack_hip
 EXPORTS = [
     "extrack_abi_version", "extrack_create", "extrack_destroy", "extrack_last_error", "extrack_set_stream",
     "extrack_upload_bucket", "extrack_attach_bucket", "extrack_set_bucket_dt", "extrack_clear_buckets", "extrack_bucket_count",
-    "extrack_loglik", "extrack_loglik_async", "extrack_predict", "extrack_last_kernel_ms",
+    "extrack_loglik", "extrack_loglik_async", "extrack_predict", "extrack_map_states", "extrack_last_kernel_ms",
     "extrack_last_launch_info", "extrack_p_stay_table", "extrack_loglik_th", "extrack_loglik_th_async", "extrack_th_plan_step",
     "extrack_predict_th", "extrack_loglik_grad", "extrack_loglik_grad_async", "extrack_loglik_scores", "extrack_loglik_scores_async", "extrack_last_grad_ms", "extrack_segment_len_hist", "extrack_refine_positions",
     "extrack_refine_pos_pdf",
@@ -102,6 +102,7 @@ def load():
     lib.extrack_loglik.argtypes = [vp, C.POINTER(ExtrackModel), _dp, vp]
     lib.extrack_loglik_async.argtypes = [vp, C.POINTER(ExtrackModel), vp]
     lib.extrack_predict.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
+    lib.extrack_map_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_last_launch_info.argtypes = [vp, C.POINTER(i32 * 6)]
     lib.extrack_p_stay_table.argtypes = [vp, i32, i32, vp, i32, vp]
@@ -438,6 +439,16 @@ class Context:
         out = np.empty((N, L, model.c.n_states))
         self._check(self._lib.extrack_predict(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def map_states(self, model, bucket_id, scores=False):
+        """Most-likely state path of every track of one bucket (extrack_map_states): int8 [N, L], and with ``scores`` the log joint
+        density of track and path, float64 [N]."""
+        N, L, D, KS = self.buckets[bucket_id]
+        out = np.empty((N, L), dtype=np.int8)
+        sc = np.empty(N) if scores else None
+        self._check(self._lib.extrack_map_states(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p),
+                                                 sc.ctypes.data_as(C.c_void_p) if scores else None))
+        return (out, sc) if scores else out
 
     def sequence_matrix(self, model, bucket_id):
         """LP[N, nB]: log-probability of every sequence of states still distinguished at the last position, in the reference's column

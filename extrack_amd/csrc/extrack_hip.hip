@@ -241,6 +241,7 @@ extern "C" int extrack_clear_buckets(extrack_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& b : ctx->buckets) xt_free_bucket(b);
     ctx->buckets.clear();
+    xt_map_release(ctx);  // sized by the buckets that just went (extrack_destroy comes through here too)
     return EXTRACK_OK;
 }
 

@@ -358,6 +358,10 @@ struct extrack_ctx {
     // evaluation left in the buckets; per launch group (keyed by its first bucket and size) the sequence counts that size the apply / gradient launch
     double* d_big_ws = nullptr;  // per-wavefront sequence state of the global-memory kernel for big models (xt_big.h)
     size_t big_ws_cap = 0;       // doubles
+    void* d_map_ws = nullptr;    // state-path decoder (xt_map.h): back-pointer words of the launched grid when they do not live in LDS
+    size_t map_ws_cap = 0;       // bytes
+    void* d_map_out = nullptr;   // ... its device outputs ([N] scores, [N][L] states), kept between calls
+    size_t map_out_cap = 0;      // bytes
     bool th_frozen = false;  // the per-bucket sequence counts that size the apply / gradient launch: XtBucket::th_maxG, th_sumE
     std::vector<double> blob_host;  // model tables of the current fixed-window evaluation (xt_prepare)
     bool th_plan_threads_forced = false;
@@ -408,4 +412,5 @@ int xt_th_plan_groups(extrack_ctx* ctx, const extrack_model* m, double threshold
 // column sums of per-block partials [nrows][ncol] (extrack_grad.hip): column 0 -> *ll_dst, column 1 + i -> out[i]
 void xt_grad_reduce_launch(hipStream_t st, const double* partials, int nrows, int ncol, double* ll_dst, double* out);
 void xt_rev_project(hipStream_t st, const double* adj, const double* dblob, int TB, int n_dir, double* out);  // out[i] = <adj, dblob[i]>
+void xt_map_release(extrack_ctx* ctx);  // extrack_map.hip: frees the decoder's scratch and output buffers (extrack_clear_buckets, extrack_destroy)
 const void* xt_gradr_kernel_ptr(int G, int D, int K, int NPC);  // extrack_gradr.hip: register-resident gradient kernels (xt_gradr.h), NPC = 3 | 4

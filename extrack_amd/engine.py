@@ -210,5 +210,10 @@ class TrackSet:
         """Posteriors for every uploaded bucket, in upload order: list of arrays [N_l, l, S]."""
         return [self.ctx.predict(model, i) for i in range(len(self.shapes))]
 
+    def map_states(self, model, scores=False):
+        """Most-likely state path for every uploaded bucket, in upload order: list of int8 arrays [N_l, l]; with ``scores`` a list of
+        (states, float64 [N_l] log joint density of track and path)."""
+        return [self.ctx.map_states(model, i, scores=scores) for i in range(len(self.shapes))]
+
     def close(self):
         self.ctx.close()

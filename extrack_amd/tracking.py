@@ -735,3 +735,40 @@ def predict_Bs(all_tracks, dt, params, cell_dims=[1], nb_states=4, frame_len=5, 
     finally:
         ts.close()
     return out
+
+
+def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len=6, input_LocErr=None, return_scores=False, device=None,
+                   fusion="window"):
+    """Most-likely sequence of states of every track (windowed Viterbi decoding; the reference has no such function - its users take the
+    per-position argmax of ``predict_Bs``, extrack/tracking.py:792-906, which is no sequence the model scored as a whole).
+
+    Returns {str(len): int8 ndarray[n_tracks, len]} keyed by every input key (arrays of shape (0, len) for empty buckets), rows in input
+    order; with ``return_scores`` also {str(len): float64 ndarray[n_tracks]}, the log joint density of each track and its path.
+    The recursion is that of ``predict_Bs(fusion="window")`` with sums over sequences replaced by selections: exact for tracks of at most
+    frame_len + 1 positions, and the most probable survivor of every group of sequences older than frame_len states otherwise.
+    ``nb_substeps`` is 1 and min / max length come from all keys, as in ``predict_Bs``.  A track with a NaN position or error gets states
+    -1 and score NaN."""
+    if not is_parameters(params):
+        raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")
+    if _check_fusion(fusion):
+        raise NotImplementedError("predict_states decodes the fixed-window recursion only: use fusion='window'")
+    if isinstance(dt, dict):
+        raise NotImplementedError("predict_states is not built for per-track time steps (dt as a dict of arrays)")
+    keys, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
+    le, Ds, Fs, TrMat, pBL, so = _extract_arrays(params, dt, 1, 1)
+    ds = np.sqrt(2 * Ds * dt)
+    states = {l: np.empty((0, int(l)), dtype=np.int8) for l in keys}
+    scores = {l: np.empty(0) for l in keys}
+    if tracks:
+        ts = TrackSet(tracks, sigmas, device=_resolve_device(device, None), min_len=max(int(keys[0]), 2), max_len=int(keys[-1]))
+        try:
+            if sigmas is not None:
+                model = ts.make_model(None, ds, Fs, TrMat, pBL, cell_dims, 1, frame_len, slope_offset=so)
+            else:
+                model = ts.make_model(le[None, None], ds, Fs, TrMat, pBL, cell_dims, 1, frame_len)
+            for arr, (st, sc) in zip(tracks, ts.map_states(model, scores=True)):
+                states[str(arr.shape[1])] = st
+                scores[str(arr.shape[1])] = sc
+        finally:
+            ts.close()
+    return (states, scores) if return_scores else states

@@ -15,6 +15,9 @@
  *   extrack_predict
  *       P_Cs_inter_bound_stats(..., do_preds=1)[2] for one bucket (Pool_star_P_inter,
  *       extrack/tracking_0.py:460-461, driven by predict_Bs :463-563).
+ *   extrack_map_states
+ *       nothing in the reference: the most-likely state sequence of every track of one bucket (windowed Viterbi decoding of the same
+ *       recursion), for the callers of predict_Bs (extrack/tracking.py:792-906) that segment tracks by the argmax of its posteriors.
  *   extrack_loglik_th
  *       the same sum for the THRESHOLD-FUSION kernel that extrack.tracking calls in v1.6.3: Proba_Cs
  *       (extrack/tracking.py:769-787) -> P_Cs_inter_bound_stats_th (:427-650) + fuse_tracks_th (:652-743),
@@ -148,6 +151,18 @@ int extrack_sequence_matrix(extrack_ctx* ctx, const extrack_model* model, int32_
 /* State posteriors of one bucket: preds host [n][len][S].  model->nb_substeps must be 1
  * (predict_Bs forces it, extrack/tracking.py:839). */
 int extrack_predict(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double* preds);
+
+/* Most-likely state path of every track of one bucket (windowed Viterbi decoding): states host [n][len] (int8, the state of every
+ * position), score host [n] or NULL (log joint density of the track and that path).  Replaces nothing in the reference, which has no
+ * such function; it sits beside predict_Bs (extrack/tracking.py:792-906), whose callers segment tracks by the per-position argmax of the
+ * posteriors.  The recursion is that of extrack_predict with every sum over sequences replaced by a selection: a sequence older than
+ * frame_len states survives only as the most probable member of its group, the last position takes the most probable of the
+ * n_states^(frame_len + 1) sequences left (with isBL the state after the last position is summed out), and the older states follow from
+ * the recorded choices.  For len <= frame_len + 1 the path is the exact maximiser of the sequence matrix (extrack_sequence_matrix).
+ * A track with a NaN position or error gets states -1 and score NaN.  model->nb_substeps must be 1.  EXTRACK_E_UNSUPPORTED (decided on
+ * the host, nothing is launched): n_states > 4, n_states^(frame_len - 1) > 1024 or a sequence state beyond the LDS of a CU, buckets
+ * with per-track time steps.  extrack_last_kernel_ms covers the launch. */
+int extrack_map_states(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int8_t* states, double* score);
 
 /* Tangent of a model along one direction theta: d(field)/d(theta) for every differentiable field of extrack_model.
  * The diffusion lengths enter as the derivative of their SQUARES (ds^2 = 2 D dt is what the recursion uses, and it keeps the
