@@ -17,7 +17,7 @@ EXPORTS = [
     "extrack_loglik", "extrack_loglik_async", "extrack_predict", "extrack_map_states", "extrack_last_kernel_ms",
     "extrack_last_launch_info", "extrack_p_stay_table", "extrack_loglik_th", "extrack_loglik_th_async", "extrack_th_plan_step",
     "extrack_predict_th", "extrack_loglik_grad", "extrack_loglik_grad_async", "extrack_loglik_scores", "extrack_loglik_scores_async", "extrack_last_grad_ms", "extrack_segment_len_hist", "extrack_refine_positions",
-    "extrack_refine_pos_pdf",
+    "extrack_refine_pos_pdf", "extrack_refine_fixed_states",
     "extrack_sequence_columns", "extrack_sequence_matrix", "extrack_loglik_th_grad", "extrack_loglik_th_grad_async", "extrack_th_freeze_plan", "extrack_sequence_matrix_th",
     "extrack_multi_create", "extrack_multi_destroy", "extrack_multi_last_error", "extrack_multi_device_count", "extrack_multi_uses_rccl",
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
@@ -117,6 +117,7 @@ def load():
     lib.extrack_segment_len_hist.argtypes = [vp, C.POINTER(ExtrackModel), i32, i32, vp]
     lib.extrack_refine_positions.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, vp]
     lib.extrack_refine_pos_pdf.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, i64, vp, vp, vp]
+    lib.extrack_refine_fixed_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp, vp, vp]
     lib.extrack_last_grad_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_sequence_columns.argtypes = [i32, i32, i32, i32, i32]
     lib.extrack_sequence_columns.restype = i64
@@ -393,6 +394,23 @@ class Context:
         return ([np.ascontiguousarray(cut(means, k).transpose(1, 0, 2)) for k in range(L)],
                 [np.ascontiguousarray(cut(stds, k).T)[:, :, None] for k in range(L)],
                 [np.ascontiguousarray(cut(logw, k).T) for k in range(L)])
+
+    def refine_fixed_states(self, model, bucket_id, states, logdens=False):
+        """Positions of one bucket refined along a given state path (extrack_refine_fixed_states): ``states`` int8 [n, len] (a row with a
+        negative entry gives NaN outputs) -> posterior means [n, len, dims] and stds [n, len, K] (K = 1, or dims with per-dimension
+        errors), and with ``logdens`` the log density [n] of each track's displacements given its path."""
+        N, L, D, KS = self.buckets[bucket_id]
+        states = np.asarray(states)
+        if states.dtype != np.int8 or states.shape != (N, L):
+            raise ValueError("states must be an int8 array [n_tracks, len] matching the bucket")
+        states = np.ascontiguousarray(states)
+        K = KS if model.c.locerr_mode else int(model.c.locerr_dims)
+        mu, sg = np.empty((N, L, D)), np.empty((N, L, K))
+        ld = np.empty(N) if logdens else None
+        self._check(self._lib.extrack_refine_fixed_states(self._h, C.byref(model.c), int(bucket_id), states.ctypes.data_as(C.c_void_p),
+                                                          mu.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p),
+                                                          ld.ctypes.data_as(C.c_void_p) if logdens else None))
+        return (mu, sg, ld) if logdens else (mu, sg)
 
     def last_grad_ms(self):
         ms = C.c_float(0)

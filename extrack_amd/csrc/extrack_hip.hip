@@ -242,6 +242,7 @@ extern "C" int extrack_clear_buckets(extrack_ctx* ctx)
     for (auto& b : ctx->buckets) xt_free_bucket(b);
     ctx->buckets.clear();
     xt_map_release(ctx);  // sized by the buckets that just went (extrack_destroy comes through here too)
+    xt_cond_release(ctx);
     return EXTRACK_OK;
 }
 

@@ -362,6 +362,8 @@ struct extrack_ctx {
     size_t map_ws_cap = 0;       // bytes
     void* d_map_out = nullptr;   // ... its device outputs ([N] scores, [N][L] states), kept between calls
     size_t map_out_cap = 0;      // bytes
+    void* d_cond_buf = nullptr;  // fixed-state smoother (xt_cond.h): device copies of its states input and mu / sigma / logdens outputs, kept between calls
+    size_t cond_cap = 0;         // bytes
     bool th_frozen = false;  // the per-bucket sequence counts that size the apply / gradient launch: XtBucket::th_maxG, th_sumE
     std::vector<double> blob_host;  // model tables of the current fixed-window evaluation (xt_prepare)
     bool th_plan_threads_forced = false;
@@ -413,4 +415,5 @@ int xt_th_plan_groups(extrack_ctx* ctx, const extrack_model* m, double threshold
 void xt_grad_reduce_launch(hipStream_t st, const double* partials, int nrows, int ncol, double* ll_dst, double* out);
 void xt_rev_project(hipStream_t st, const double* adj, const double* dblob, int TB, int n_dir, double* out);  // out[i] = <adj, dblob[i]>
 void xt_map_release(extrack_ctx* ctx);  // extrack_map.hip: frees the decoder's scratch and output buffers (extrack_clear_buckets, extrack_destroy)
+void xt_cond_release(extrack_ctx* ctx);  // extrack_cond.hip: frees the smoother's input / output buffer (same callers)
 const void* xt_gradr_kernel_ptr(int G, int D, int K, int NPC);  // extrack_gradr.hip: register-resident gradient kernels (xt_gradr.h), NPC = 3 | 4

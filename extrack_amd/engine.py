@@ -215,5 +215,13 @@ class TrackSet:
         (states, float64 [N_l] log joint density of track and path)."""
         return [self.ctx.map_states(model, i, scores=scores) for i in range(len(self.shapes))]
 
+    def refine_fixed_states(self, model, states_per_bucket, logdens=False):
+        """Positions refined along given state paths for every uploaded bucket, in upload order: ``states_per_bucket`` a list of int8
+        arrays [N_l, l] (what ``map_states`` returns) -> list of (means [N_l, l, D], stds [N_l, l, K]), with ``logdens`` of
+        (means, stds, log density [N_l] of the track's displacements given its path)."""
+        if len(states_per_bucket) != len(self.shapes):
+            raise ValueError("one state array per uploaded bucket is required")
+        return [self.ctx.refine_fixed_states(model, i, st, logdens=logdens) for i, st in enumerate(states_per_bucket)]
+
     def close(self):
         self.ctx.close()

@@ -37,6 +37,11 @@
  *   extrack_refine_pos_pdf
  *       get_pos_PDF's own return values (extrack/refined_localization.py:207-298): means / stds / log-weights of every component of the
  *       Gaussian mixture of every position, for inspection of small buckets.
+ *   extrack_refine_fixed_states
+ *       what get_pos_PDF_fixedBs / get_LC_Km_Ks_fixed_Bs (extrack/refined_localization.py:414-519, used by get_best_estimates :551-560)
+ *       were written to compute: mean and std of every real position given ONE state per position.  Not that function's numbers, which
+ *       are inconsistent as shipped: it hands standard deviations to the variance-based integrals it imports from tracking_0 (:27) and
+ *       squares their results again (:446, :460, :471), pairs all_Km1[-k] with all_Ks1[-1-k] (:505-506) and reads track 0 only (:478-480).
  *   extrack_loglik_grad
  *       extrack_loglik AND its exact gradient in one pass.  It replaces the finite-difference loop that the reference's
  *       optimiser runs around cum_Proba_Cs (lmfit.minimize at extrack/tracking.py:1371: BFGS evaluates the objective
@@ -275,6 +280,22 @@ int extrack_refine_positions(extrack_ctx* ctx, const extrack_model* model, int32
  * (EXTRACK_REFINE_BUDGET_MB), EXTRACK_E_UNSUPPORTED otherwise - the components of a large bucket are not meant to leave the GPU. */
 int extrack_refine_pos_pdf(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double threshold, int32_t max_nb_states,
                            int32_t* counts, int64_t capacity, double* means, double* stds, double* logw);
+
+/* Positions of one bucket refined along a given state path (fixed-state smoother, csrc/xt_cond.h): states host [n][len] (int8, the state
+ * of every position, as extrack_map_states writes them), mu host [n][len][dims], sigma host [n][len][K] with K = 1 (one error for all
+ * dimensions) or dims (locerr_dims = dims, or per-peak errors uploaded per dimension), logdens host [n] or NULL.  Model of one track, per
+ * dimension: flat prior on the first real position, real steps N(0, q[t]) with q[t] = (ds[b[t]]^2 + ds[b[t+1]]^2) / 2 - the step variance
+ * of the likelihood's tables -, observations N(real position, error^2) with the error of locerr_mode 0 / 1 / 2.  mu / sigma: posterior mean
+ * and standard deviation of every real position given the whole track and the path; logdens: log density of the len - 1 observed
+ * displacements given the path (the path's own prior - Fs, TrMat, p_stay, pBL - is not part of it, and none of those fields is read;
+ * frame_len, min_len, max_len are not used either).  Any n_states in 2..8, dims 1..3, every track length.  A track with a NaN position or
+ * error, or with a negative state (extrack_map_states writes -1 for such tracks), is NaN in all three outputs.  Decided on the host,
+ * nothing launched: EXTRACK_E_INVALID for nb_substeps != 1 and for a state >= n_states anywhere; EXTRACK_E_UNSUPPORTED for buckets with
+ * per-track time steps.  Rows of 64 tracks live in LDS while they fit a CU, else in mu / sigma themselves (EXTRACK_COND_WS=global forces
+ * that; extrack_last_launch_info then reports the LDS bytes of the step-variance table alone, 8 * n_states^2 rounded up to 16); both give
+ * the same bits.  extrack_last_kernel_ms and extrack_last_launch_info cover the launch. */
+int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, const int8_t* states, double* mu,
+                                double* sigma, double* logdens);
 
 /* Threshold-fusion log-likelihood (the kernel extrack.tracking.param_fitting / cum_Proba_Cs call in v1.6.3,
  * extrack/tracking.py:427-743).  Which state sequences are merged at a step is decided from the first 30 tracks
