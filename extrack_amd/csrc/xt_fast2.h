@@ -112,8 +112,14 @@ XT_HD void xt_exp_tab_x1(double x, double& p, int& j, int& e)
     const double k = t - XT_MAGIC;
     double r = xt_fma(k, XT_F2_EXP_HI, x);
     r = xt_fma(k, XT_F2_EXP_LO, r);
-    double q = 1.66666666666666666667e-01;
-    q = xt_fma(q, r, XT_F2_EXP_C2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // the cubic's first fma as ONE three-operand instruction, 1/6 from a scalar register: the compiler writes it as a 64-bit move of c2 and an
+    // accumulating fma
+    double q;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(q) : "s"(1.66666666666666666667e-01), "v"(r), "v"(XT_F2_EXP_C2));
+#else
+    double q = xt_fma(1.66666666666666666667e-01, r, XT_F2_EXP_C2);
+#endif
     q = xt_fma(q, r, 1.0);
     p = xt_fma(q, r, 1.0);
     xt_f2_exp_bits(t, j, e);

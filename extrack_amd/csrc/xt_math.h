@@ -66,6 +66,21 @@ XT_HD double xt_rint(double x) { return nearbyint(x); }
 
 XT_HD double xt_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
+// 1 / x as xt_rcp, in THREE dependent FMA: one second-order step on the hardware seed, r (1 + e + e^2) with e = 1 - x r.  The seed is good to
+// 2^-24.4, so the truncated e^3 is ~1e-22: the result is rounded once, like xt_rcp's (measured side by side, tools/ubench/rcp_accuracy.hip,
+// profiles/r01_valu_rates.txt).  For the likelihood-only 2-state path (xt_reg2.h).
+XT_HD double xt_rcp3(double x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    double r = __builtin_amdgcn_rcp(x);
+    const double e = __builtin_fma(-x, r, 1.0);
+    const double t = __builtin_fma(e, e, e);
+    return __builtin_fma(r, t, r);
+#else
+    return 1.0 / x;
+#endif
+}
+
 // 1 / x with ONE Newton step on the hardware seed (measured 2.2e-15 relative, tools/ubench/rcp_accuracy.hip): for quantities that end in a
 // normalised posterior (tolerance 1e-9), not in the likelihood.
 XT_HD double xt_rcp_fast(double x)

@@ -64,7 +64,7 @@ XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw)
 }
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
 // Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
-// ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2), 2 l2} and lnT'[v][prev][q] = ln TAB[v][prev][q] - D/2 ln l2, v = 0 (T), 1 (T * stay)
+// ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2) (kept in the map; the ratio form of the step no longer reads it), 2 l2} and lnT'[v][prev][q] = ln TAB[v][prev][q] - D/2 ln l2, v = 0 (T), 1 (T * stay)
 // - at a fixed distance from the entry of table v, so that the step reaches it from the same `tab + [prev][q]` address.
 #define XT_R2_GC_OFF 800
 #define XT_R2_LNT_OFF 960
@@ -317,7 +317,11 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 //     u_q = l2 (1 - g_q)       =>  the members carry v = l2 + u:  v_q = 2 l2 - l2 g_q,  W den_q = Ws d2_q + V  (no l2 + d2 add)
 //     den_q^(-D/2) = (g_q / l2)^(D/2),  -|c - m_bar|^2 / (2 den_q) = A g_q  with  A = -|c - m_bar|^2 / (2 l2)
 //     weight_q = Wm g_q^(D/2) exp(A g_q + lnT'[prev][q]),  lnT' = ln T - D/2 ln l2   (table built per workgroup: no T multiply, no gf)
-// The shared reciprocal R = 1 / (Ws Dq0 Dq1) stays: 1 / W = R Dq0 Dq1 and g_q = (R Ws^2 l2) Dq[1 - q].
+// RATIO FORM: none of 1 / W, g_q or c - m_bar is formed.  With Dq_q = Ws d2_q + V = W den_q, the shared reciprocal R = 1 / (Ws Dq0 Dq1)
+// (xt_rcp3) gives h_q = R Dq[1 - q] = 1 / (Ws Dq_q) directly, and everything is written on the un-normalised e_d = c_d Ws - M_d = Ws (c - m_bar)_d:
+//     A g_q = (-1/2 sum_d e_d^2) h_q                              (|c - m_bar|^2 / den_q = (sum e_d^2 / Ws^2) (Ws / Dq_q); no -1 / (2 l2) constant)
+//     k_q = (l2 Ws) h_q = l2 / Dq_q = g_q / Ws   =>   m_q = c - e_d k_q,   v_q = 2 l2 - (l2 Ws) k_q
+//     y_q = Wm (Ws k_q)^(D/2);  D = 2:  y_q = (Wm Ws) k_q         (FIRST: Ws = 1, so h_q = R Dq[1 - q], k_q = l2 h_q, e_d = c_d - m_d)
 // A member's weight is y exp(lx) (s.z = y, a lazily normalised double; lx, a double next to the lane state; s.e is not used): the child's exponential is never
 // taken - lx_q = A g_q + lnT'[prev][q] + base, y_q = Wm g_q^(D/2).  The merge of the NEXT step needs only the ratio of its two members,
 // ONE exponential E = exp(-|lx1 - lx0|) (xt_exp_tab_x1 with its clamp: E = 0 beyond 1.1e7, where the magic-number reduction would leave its
@@ -326,8 +330,10 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 // the integer exponent bookkeeping) the merge grows by the one exponential and two selects.
 // Lazy re-normalisation (every XT_F2_RENORM-th phase): Wm = frexp_mant(Ws), base += ln2 frexp_exp(Ws).  Range of the lazy mantissa:
 // y = Wm g^(D/2) with g = l2 / den in [1e-16, 1] (well-scaled bounds: l2 >= 1e-12, den <= 1e4) and a merge at most doubles the sum
-// (E <= 1): three un-normalised steps stay within [1e-72, 8]; the products of a step are then W^3 den^2 >= 1e-240 and
-// R Ws^2 l2 <= 1e264 * 1e4 - the transition weight and l2^(-D/2) live in lx.
+// (E <= 1): three un-normalised steps stay within [1e-72, 8]; the products of a step are then Ws Dq0 Dq1 = W^3 den^2 >= 1e-240 (<= 8^3 * 1e8),
+// h_q = 1 / (W^2 den_q) <= 1 / (W_min den_min W_min) = 1e144 * 1e12, k_q = l2 h_q Ws <= 1 / W_min = 1e72 (g_q <= 1), e_d^2 <= 64 |c - m_bar|^2,
+// sum e_d^2 h_q = |c - m_bar|^2 / den_q is the same number as before, and Wm Ws <= 64, >= 1e-144 (Wm = Ws between re-normalisations) - all
+// far inside the fp64 range; the transition weight and l2^(-D/2) live in lx.
 // Re-centring (phase XT_R2_RC_H, once per F - 1 steps): lx is rounded at ulp(|lx|), so it must not grow with the accumulated
 // log-likelihood.  The lanes of a track take the maximum of their truncated bases through an integer atomic max on the track's LDS cell
 // (LDS and cx.wave_sync() only): sh, an integer common to the track.  base -= sh (exact, or one rounding at the ulp of the small
@@ -343,22 +349,62 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 #define XT_R2_RC_H 0  // re-centring phase: a re-normalisation phase
 #endif
 #define XT_R2_RC_NONE (-2147483647 - 1)
-template <int F, int D, int H, bool FIRST = false, class Ctx>
-XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2], int tab, const double* c)
+// The [prev][q] table byte offset of a lane's first output, (prev * 2 + qa) * 8 (xt_r2_step), is a per-lane constant of the phase: all F - 1 of
+// them packed into one word, 5 bits per phase, built once per kernel.  The step extracts its field (the second output's offset is that ^ 8)
+// instead of deriving both from the lane id with shifts, ands and bit insertions in every step.
+#define XT_R2_IO_BITS 5
+template <int F, int H, class Ctx>
+XT_HD int xt_r2_pack_io(int lane)
 {
     constexpr int NGB = F - 1;
-    constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
-    const int lane = xt_opaque(cx.lane());
-    const int prev = (lane >> PB) & 1;
-    const int qa = Ctx::template pair_natural<XB>() ? 0 : (lane >> XB) & 1;
-    const int io[2] = {(prev * 2 + qa) * 8, (prev * 2 + (qa ^ 1)) * 8};
+    if constexpr (H >= NGB) {
+        return 0;
+    } else {
+        constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
+        const int prev = (lane >> PB) & 1;
+        const int qa = Ctx::template pair_natural<XB>() ? 0 : (lane >> XB) & 1;
+        return ((prev * 2 + qa) * 8) << (XT_R2_IO_BITS * H) | xt_r2_pack_io<F, H + 1, Ctx>(lane);
+    }
+}
+// In-place barrier on the packed word: the compiler cannot hoist the 2 (F - 1) extracted offsets out of the step loop into registers of their
+// own (as xt_opaque does for the lane id), and no copy of the word is made.
+XT_HD void xt_r2_opaque_inplace(int& pk)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(pk));
+#else
+    (void)pk;
+#endif
+}
+// 8 * tid, the byte offset of the thread's re-centring cells, formed where it is used: the shift is the barrier itself (no copy of the thread id as
+// xt_opaque makes, and nothing for the compiler to keep in a register across the step loop).
+template <class Ctx>
+XT_HD int xt_r2_tid8(Ctx& cx)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int o;
+    asm volatile("v_lshlrev_b32 %0, 3, %1" : "=v"(o) : "v"(cx.tid()));
+    return o;
+#else
+    return cx.tid() * 8;
+#endif
+}
+template <int F, int D, int H, bool FIRST = false, class Ctx>
+XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2], int& pk, int tab, const double* c)
+{
+    constexpr int NGB = F - 1;
+    constexpr int XB = xt_r2_gbit(F, H);
+    xt_r2_opaque_inplace(pk);
+    int io0 = (int)(((unsigned int)pk >> (XT_R2_IO_BITS * H)) & ((1u << XT_R2_IO_BITS) - 1u));
+    xt_r2_opaque_inplace(io0);  // the second offset from the extracted field (one xor), not from the word again (a shift and a three-input bit operation)
+    const int io[2] = {io0, io0 ^ 8};
     double TD2[2], LT[2];
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
         TD2[q] = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + io[q]);
         LT[q] = xt_at<double>(lds, tab + XT_R2_LNT_REL + io[q]);
     }
-    const double l2 = xt_at<double>(lds, 0), nh = xt_at<double>(lds, XT_R2_GC_OFF), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
+    const double l2 = xt_at<double>(lds, 0), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
 
     // ---- merge (members carry v = l2 + u): the member with the smaller lx is scaled by exp(-|lx1 - lx0|)
     double w0 = 1.0, w1 = 0.0, base = lx[0];
@@ -384,39 +430,39 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2
     if (!FIRST && H == XT_R2_RC_H) {
         // re-centring: the integer shift is the largest (truncated) base among the track's lanes - an atomic max on the track's LDS cell,
         // which every lane of the track reset one phase later in the previous pass (or at position 0)
-        const int tid = xt_opaque(cx.tid());
+        const int tid8 = xt_r2_tid8(cx);
         const int rc0 = xt_r2_rc0(D, 0, XtR2Geom<F>::TPW);  // g-form launches stage no per-peak errors (KS = 0)
-        const int cell = rc0 + (tid & ~xt_r2_gmask(F)) * 8;
+        const int cell = rc0 + (tid8 & ~(xt_r2_gmask(F) * 8));
         cx.atomic_max_i32(&xt_at<int>(lds, cell), (int)fmin(fmax(base, -1e9), 1e9));  // a NaN base (poisoned track) counts as -1e9
         cx.wave_sync();
         const int sh = xt_at<int>(lds, cell);
         base -= (double)sh;
-        xt_at<unsigned int>(lds, rc0 + XT_R2_RC_ARR + tid * 8) += (unsigned int)sh;  // read back as int; wraps only on a poisoned track (-1e9 per pass)
+        xt_at<unsigned int>(lds, rc0 + XT_R2_RC_ARR + tid8) += (unsigned int)sh;  // read back as int; wraps only on a poisoned track (-1e9 per pass)
     }
-    if (!FIRST && H == (XT_R2_RC_H + 1) % NGB) xt_at<int>(lds, xt_r2_rc0(D, 0, XtR2Geom<F>::TPW) + (xt_opaque(cx.tid()) & ~xt_r2_gmask(F)) * 8) = XT_R2_RC_NONE;
+    if (!FIRST && H == (XT_R2_RC_H + 1) % NGB) xt_at<int>(lds, xt_r2_rc0(D, 0, XtR2Geom<F>::TPW) + (xt_r2_tid8(cx) & ~(xt_r2_gmask(F) * 8))) = XT_R2_RC_NONE;
 
-    // ---- the shared reciprocal, g_q
+    // ---- the shared reciprocal, h_q and k_q
     const double Dq0 = xt_fma(Ws, TD2[0], V), Dq1 = xt_fma(Ws, TD2[1], V);
-    const double d01 = Dq0 * Dq1;
-    const double R = xt_rcp(Ws * d01);
-    const double rW = FIRST ? 1.0 : R * d01;
-    const double G = R * (Ws * (Ws * l2));
-    const double g[2] = {G * Dq1, G * Dq0};
-    double dn[D], dsq = 0.0;
+    const double R = xt_rcp3(Ws * (Dq0 * Dq1));
+    const double h[2] = {R * Dq1, R * Dq0};
+    const double l2W = FIRST ? l2 : l2 * Ws;
+    double ed[D], esq = 0.0;
     XT_UNROLL
     for (int d = 0; d < D; ++d) {
-        dn[d] = xt_fma(c[d], Ws, -M[d]) * rW;  // c - m_bar
-        dsq = xt_fma(dn[d], dn[d], dsq);
+        ed[d] = FIRST ? c[d] - M[d] : xt_fma(c[d], Ws, -M[d]);  // Ws (c - m_bar)
+        esq = xt_fma(ed[d], ed[d], esq);
     }
-    const double A = dsq * nh;
+    const double Ah = -0.5 * esq;
+    const double WmW = FIRST ? Wm : Wm * Ws;
     double ny[2], nl[2], nm[2][D], nv[2];
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
-        ny[q] = Wm * xt_pow_half<D>(g[q]);
-        nl[q] = xt_fma(A, g[q], LT[q]) + base;
+        const double k = l2W * h[q];
+        ny[q] = D == 2 ? WmW * k : Wm * xt_pow_half<D>(FIRST ? k : Ws * k);
+        nl[q] = xt_fma(Ah, h[q], LT[q]) + base;
         XT_UNROLL
-        for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(-dn[d], g[q], c[d]);
-        nv[q] = xt_fma(-l2, g[q], l22);
+        for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(-ed[d], k, c[d]);
+        nv[q] = xt_fma(-l2W, k, l22);
     }
     cx.template pair_exchange<XB>(ny[0], ny[1]);
     cx.template pair_exchange<XB>(nl[0], nl[1]);
@@ -488,7 +534,7 @@ XT_HD void xt_r2_chain(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int T, int sta
         XT_UNROLL
         for (int k = 0; k < K; ++k) {
             const double a = d2 + s.u[0][k];
-            r[k] = xt_rcp(l2[k] + a);
+            r[k] = NP == 0 ? xt_rcp3(l2[k] + a) : xt_rcp(l2[k] + a);
             tt[k] = a * r[k];
         }
         XT_UNROLL
@@ -580,11 +626,17 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     double l2g[K];
     XT_UNROLL
     for (int k = 0; k < K; ++k) l2g[k] = hdr[k];
+    // g-form steps: the [prev][q] table offsets of this lane's outputs in all F - 1 phases (xt_r2_pack_io), kept across the step loop instead of
+    // the lane id
+    int pk = xt_r2_pack_io<F, 0, Ctx>(lane);
     const bool well_scaled = a.well_scaled != 0;
     const bool chain = NP == 0 && well_scaled;  // warm-up as per-lane chains (xt_r2_chain)
 
     double* pos = (double*)(lds + xt_r2_pos0(NPT)) + wib * TPW * XT_F2_CHUNK * (D + KS);  // [TPW][CHUNK][D]
     double* sig = pos + TPW * XT_F2_CHUNK * D;                                           // [TPW][CHUNK][KS]
+    // likelihood only: the byte address of this lane's staged positions as ONE opaque per-lane word (the compiler otherwise keeps the constant
+    // base of the array apart from the per-lane part and adds it in every step)
+    const int posb = NP == 0 ? xt_opaque(xt_r2_pos0(0) + (wib * TPW * XT_F2_CHUNK * (D + KS) + ts * XT_F2_CHUNK * D) * 8) : 0;
     // per (wave, track slot): NP == 0 {mantissa, exponent, count} of the running likelihood product; NP > 0 {sum LL, sum dLL_p}
     double* accp = (double*)(lds + xt_r2_acc0(NPT, D, KS, TPW)) + (wib * 8 + ts) * (NPT + 3);
     // NP == 0 reaches them by a byte address formed where it is used, as the re-centring cells below: nothing more is kept in registers
@@ -641,7 +693,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         auto getpos = [&](int t, double* c, double* l2) XT_INL {
             const int r = t & (XT_F2_CHUNK - 1);
             XT_UNROLL
-            for (int d = 0; d < D; ++d) c[d] = pos[(ts * XT_F2_CHUNK + r) * D + d];
+            for (int d = 0; d < D; ++d) c[d] = NP == 0 ? xt_at<double>(lds, posb + (r * D + d) * 8) : pos[(ts * XT_F2_CHUNK + r) * D + d];
             if (KS == 0) {
                 XT_UNROLL
                 for (int k = 0; k < K; ++k) l2[k] = xt_at<double>(lds, k * 8);  // broadcast read of the blob header (two fewer live VGPRs per k than a register copy)
@@ -672,7 +724,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
         getpos(t, c, l2);                                                                              \
-        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lx, XT_R2_TABSEL, c);                        \
+        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lx, pk, XT_R2_TABSEL, c);                    \
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
@@ -783,7 +835,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                                 if (gform) {  // from here on the members carry v = l2 + u and weights y exp(lx) (until the read-out of the last position)
                                     s.u[0][0] += l2[0];
                                     lx[0] = (double)s.e[0] * XT_LN2;
-                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lx, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
+                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lx, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
                                     s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lx now
                                     first_done = true;
                                 }
@@ -815,6 +867,20 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int prev = (lane >> pbit) & 1;
             double wm[4], rr[4][K], dq[2][D], dsqQ[2];
             int we[4];
+            if constexpr (NP == 0 && K == 1) {
+                // the four 1 / den of the (Q, q) pairs from ONE reciprocal of their product (den in [1e-12, 1e4] on a well-scaled launch, and
+                // any launch's variances are far from the fp64 range limits: xt_rcp)
+                double dn[4];
+                XT_UNROLL
+                for (int i = 0; i < 4; ++i) dn[i] = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + (prev * 2 + (i & 1)) * 8) + s.u[i >> 1][0] + l2l[0];
+                const double p01 = dn[0] * dn[1], p23 = dn[2] * dn[3];
+                const double R = xt_rcp3(p01 * p23);
+                const double r01 = R * p23, r23 = R * p01;  // 1 / (dn0 dn1), 1 / (dn2 dn3)
+                rr[0][0] = r01 * dn[1];
+                rr[1][0] = r01 * dn[0];
+                rr[2][0] = r23 * dn[3];
+                rr[3][0] = r23 * dn[2];
+            }
             XT_UNROLL
             for (int Q = 0; Q < 2; ++Q) {
                 dsqQ[Q] = 0.0;
@@ -828,8 +894,13 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 for (int q = 0; q < 2; ++q) {
                     const double d2 = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + (prev * 2 + q) * 8);
                     if (K == 1) {
-                        const double r = xt_rcp(d2 + s.u[Q][0] + l2l[0]);
-                        rr[Q * 2 + q][0] = r;
+                        double r;
+                        if constexpr (NP == 0) {
+                            r = rr[Q * 2 + q][0];
+                        } else {
+                            r = xt_rcp(d2 + s.u[Q][0] + l2l[0]);
+                            rr[Q * 2 + q][0] = r;
+                        }
                         x[q] = -0.5 * dsqQ[Q] * r;
                         if constexpr (NP == 0) x[q] += lx[Q];  // log-carried weights (xt_r2_step_g): y exp(lx), e = 0
                         gf[q] = xt_pow_half<D>(r);
@@ -837,7 +908,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         double xx = 0.0, gg = 1.0;
                         XT_UNROLL
                         for (int d = 0; d < D; ++d) {
-                            const double r = xt_rcp(d2 + s.u[Q][d] + l2l[d]);
+                            const double r = NP == 0 ? xt_rcp3(d2 + s.u[Q][d] + l2l[d]) : xt_rcp(d2 + s.u[Q][d] + l2l[d]);
                             rr[Q * 2 + q][d] = r;
                             xx = xt_fma(-0.5 * dq[Q][d] * dq[Q][d], r, xx);
                             gg *= r;
