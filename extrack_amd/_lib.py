@@ -21,6 +21,7 @@ EXPORTS = [
     "extrack_sequence_columns", "extrack_sequence_matrix", "extrack_loglik_th_grad", "extrack_loglik_th_grad_async", "extrack_th_freeze_plan", "extrack_sequence_matrix_th",
     "extrack_multi_create", "extrack_multi_destroy", "extrack_multi_last_error", "extrack_multi_device_count", "extrack_multi_uses_rccl",
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
+    "extrack_loglik_gaps", "extrack_predict_gaps",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -102,6 +103,8 @@ def load():
     lib.extrack_loglik.argtypes = [vp, C.POINTER(ExtrackModel), _dp, vp]
     lib.extrack_loglik_async.argtypes = [vp, C.POINTER(ExtrackModel), vp]
     lib.extrack_predict.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
+    lib.extrack_loglik_gaps.argtypes = [vp, C.POINTER(ExtrackModel), _dp, vp]
+    lib.extrack_predict_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
     lib.extrack_map_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_last_launch_info.argtypes = [vp, C.POINTER(i32 * 6)]
@@ -259,10 +262,12 @@ class Context:
     def n_tracks(self):
         return sum(b[0] for b in self.buckets)
 
-    def loglik(self, model, per_track=False):
+    def loglik(self, model, per_track=False, gaps=False):
+        """Sum of the per-track log-likelihoods (and, with ``per_track``, each of them).  ``gaps``: all-NaN rows are missed detections
+        (extrack_loglik_gaps) instead of poisoning their track."""
         tot = C.c_double(0.0)
         out = np.empty(self.n_tracks()) if per_track else None
-        self._check(self._lib.extrack_loglik(self._h, C.byref(model.c), C.byref(tot), out.ctypes.data_as(C.c_void_p) if per_track else None))
+        self._check((self._lib.extrack_loglik_gaps if gaps else self._lib.extrack_loglik)(self._h, C.byref(model.c), C.byref(tot), out.ctypes.data_as(C.c_void_p) if per_track else None))
         return (tot.value, out) if per_track else tot.value
 
     @staticmethod
@@ -452,10 +457,10 @@ class Context:
     def loglik_async(self, model, d_total_ptr=None):
         self._check(self._lib.extrack_loglik_async(self._h, C.byref(model.c), C.c_void_p(d_total_ptr) if d_total_ptr else None))
 
-    def predict(self, model, bucket_id):
+    def predict(self, model, bucket_id, gaps=False):
         N, L, D, KS = self.buckets[bucket_id]
         out = np.empty((N, L, model.c.n_states))
-        self._check(self._lib.extrack_predict(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p)))
+        self._check((self._lib.extrack_predict_gaps if gaps else self._lib.extrack_predict)(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def map_states(self, model, bucket_id, scores=False):

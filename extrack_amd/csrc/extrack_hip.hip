@@ -654,7 +654,7 @@ struct XtFuseTotal {
 
 static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::vector<XtBucket*>& bks, bool preds, bool per_track,
                            double* d_preds, size_t poff, size_t desc_off, int* grid_out, double* d_seq = nullptr,
-                           const XtFuseTotal* fuse = nullptr)
+                           const XtFuseTotal* fuse = nullptr, bool gaps = false)
 {
     const XtConfig& c = ctx->cfg;
     const XtBucket& b0 = *bks[0];
@@ -673,8 +673,9 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     xt_fill_args_from_config(c, l.a);
     int tpb, threads;
     // d_seq (extrack_sequence_matrix): the general kernel writes the log-weight of every sequence of the last position, without the leaving term
-    const bool fast2 = !d_seq && xt_use_fast2(c.S, c.NS, c.F, preds);
-    const bool entry = !d_seq && !fast2 && xt_use_entry(c.NS, c.G, c.NG, preds);
+    // gaps (extrack_loglik_gaps / extrack_predict_gaps): the general body's gap-aware instantiations only (extrack_gaps.hip), two states included
+    const bool fast2 = !d_seq && !gaps && xt_use_fast2(c.S, c.NS, c.F, preds);
+    const bool entry = !d_seq && !gaps && !fast2 && xt_use_entry(c.NS, c.G, c.NG, preds);
     if (entry) {
         xt_entry_geometry(c.S, c.G, c.E, c.NG, D, K, tpb, threads, l.lds);
     } else if (fast2) {
@@ -690,8 +691,9 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     // the sequence state of a track does not fit a workgroup (more than 1024 groups, more than the CU's LDS, posteriors beyond the built group
     // sizes): one lane per track with the state in global memory (xt_big.h)
     bool big = l.lds > 160 * 1024 || (!fast2 && !entry && (threads > 1024 || (preds && c.G > 6)));
-    if (const char* ev = getenv("EXTRACK_FORCE_BIG")) big = big || (atoi(ev) != 0 && !d_seq);
+    if (const char* ev = getenv("EXTRACK_FORCE_BIG")) big = big || (atoi(ev) != 0 && !d_seq && !gaps);
     XtBigArgs bargs;
+    if (big && gaps) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: the global-state kernel for big models has no gap-aware variant");
     if (big) {
         if (d_seq) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "sequence matrix: n_states^frame_len sequences per track do not fit a workgroup");
         if (preds && c.F > 15) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "posteriors: frame_len > 15");
@@ -785,6 +787,10 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
             bargs.ws = ctx->d_big_ws;
             l.enqueue(kp);
         }
+    } else if (gaps) {
+        const void* kp = xt_gap_kernel_ptr(c.NS == 1 ? c.G : 0, D, K, preds, threads > 256);
+        ok = kp != nullptr;
+        if (ok) l.launch_ptr(kp);
     } else {
         ok = fast2 ? xt_dispatch_f2(c.F, D, K, l) : (entry ? xt_dispatch_entry(xt_entry_gp(c.G), D, K, l) : xt_dispatch(c.G, D, K, preds, l));
     }
@@ -804,11 +810,36 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
 // Upper bound of the blocks of one launch (= partial-sum slots to reserve).
 size_t xt_max_grid(const extrack_ctx* ctx) { return (size_t)ctx->n_cu * 8 * ctx->oversub + XT_MAX_BUCKETS; }
 
-static int xt_loglik_enqueue(extrack_ctx* ctx, const extrack_model* m, double* d_total, bool per_track, bool to_host = false)
+// Missed detections (extrack_loglik_gaps / extrack_predict_gaps): what the gap-aware kernels (extrack_gaps.hip) do not serve is refused here, on
+// the host, before anything is enqueued or recorded.  `only`: the one bucket of a posterior call, or nullptr for all buckets.
+static int xt_gaps_check(extrack_ctx* ctx, const extrack_model* m, const XtBucket* only)
+{
+    if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: built for nb_substeps == 1");
+    if (m->n_states < 2 || m->n_states > 4) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: built for 2, 3 and 4 states");
+    XtConfig c;
+    std::string err = xt_build_config(m->n_states, m->nb_substeps, m->frame_len, c);
+    if (!err.empty()) return xt_fail(ctx, EXTRACK_E_INVALID, err);
+    for (const XtBucket& b : ctx->buckets) {
+        if (only && &b != only) continue;
+        if (b.d_dt) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: not built for buckets with per-track time steps");
+        const int D = b.D, K = m->locerr_mode == 0 ? m->locerr_dims : b.KS;
+        if (K != 1 && K != D) return xt_fail(ctx, EXTRACK_E_INVALID, m->locerr_mode == 0 ? "locerr_dims must be 1 or the track dimensionality"
+                                                                                         : "per-peak localisation error mode but the bucket has no sigma");
+        int tpb, threads;
+        xt_geometry(c, D, K, tpb, threads);
+        if (threads > 1024 || xt_lds_bytes(c, D, K, tpb) > 160 * 1024)
+            return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: n_states^frame_len sequences per track do not fit a workgroup (no gap-aware global-state kernel)");
+        if (!xt_gap_kernel_ptr(c.G, D, K, only != nullptr, threads > 256)) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: kernel variant not built");
+    }
+    return EXTRACK_OK;
+}
+
+static int xt_loglik_enqueue(extrack_ctx* ctx, const extrack_model* m, double* d_total, bool per_track, bool to_host = false, bool gaps = false)
 {
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (ctx->buckets.empty()) return xt_fail(ctx, EXTRACK_E_INVALID, "no bucket uploaded");
+    if (gaps && (rc = xt_gaps_check(ctx, m, nullptr))) return rc;
     XT_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = xt_prepare(ctx, m))) return rc;
     // launch groups: buckets with the same (dims, sigma dims), longest first, at most XT_MAX_BUCKETS per launch
@@ -839,7 +870,7 @@ static int xt_loglik_enqueue(extrack_ctx* ctx, const extrack_model* m, double* d
     XT_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     for (auto& g : groups) {
         int grid = 0;
-        if ((rc = xt_launch_group(ctx, m, g, false, per_track, nullptr, poff, doff, &grid, nullptr, fused ? &fz : nullptr))) return rc;
+        if ((rc = xt_launch_group(ctx, m, g, false, per_track, nullptr, poff, doff, &grid, nullptr, fused ? &fz : nullptr, gaps))) return rc;
         poff += (size_t)grid;
         doff += g.size();
     }
@@ -858,10 +889,10 @@ extern "C" int extrack_loglik_async(extrack_ctx* ctx, const extrack_model* model
     return xt_loglik_enqueue(ctx, model, d_total_ll ? d_total_ll : ctx->d_total, false);
 }
 
-extern "C" int extrack_loglik(extrack_ctx* ctx, const extrack_model* model, double* total_ll, double* per_track)
+static int xt_loglik_sync(extrack_ctx* ctx, const extrack_model* model, double* total_ll, double* per_track, bool gaps)
 {
     if (!ctx || !total_ll) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
-    int rc = xt_loglik_enqueue(ctx, model, ctx->d_total, per_track != nullptr, true);
+    int rc = xt_loglik_enqueue(ctx, model, ctx->d_total, per_track != nullptr, true, gaps);
     if (rc) return rc;
     if (!ctx->fused_host) XT_HIP(ctx, hipMemcpyAsync(ctx->h_total, ctx->d_total, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (per_track) {
@@ -876,12 +907,23 @@ extern "C" int extrack_loglik(extrack_ctx* ctx, const extrack_model* model, doub
     return EXTRACK_OK;
 }
 
-extern "C" int extrack_predict(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, double* preds)
+extern "C" int extrack_loglik(extrack_ctx* ctx, const extrack_model* model, double* total_ll, double* per_track)
+{
+    return xt_loglik_sync(ctx, model, total_ll, per_track, false);
+}
+
+extern "C" int extrack_loglik_gaps(extrack_ctx* ctx, const extrack_model* model, double* total_ll, double* per_track)
+{
+    return xt_loglik_sync(ctx, model, total_ll, per_track, true);
+}
+
+static int xt_predict_sync(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, double* preds, bool gaps)
 {
     if (!ctx || !preds) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (bucket_id < 0 || bucket_id >= (int)ctx->buckets.size()) return xt_fail(ctx, EXTRACK_E_INVALID, "bucket id out of range");
+    if (gaps && (rc = xt_gaps_check(ctx, m, &ctx->buckets[bucket_id]))) return rc;
     if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_INVALID, "state predictions require nb_substeps == 1");
     XT_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = xt_prepare(ctx, m))) return rc;
@@ -893,7 +935,7 @@ extern "C" int extrack_predict(extrack_ctx* ctx, const extrack_model* m, int32_t
     int grid = 0;
     hipError_t e = hipEventRecord(ctx->ev0, ctx->stream);
     std::vector<XtBucket*> one(1, &b);
-    rc = xt_launch_group(ctx, m, one, true, false, d_preds, 0, xt_desc_base(ctx), &grid);
+    rc = xt_launch_group(ctx, m, one, true, false, d_preds, 0, xt_desc_base(ctx), &grid, nullptr, nullptr, gaps);
     if (rc == EXTRACK_OK) {
         if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
         ctx->timed = true;
@@ -902,6 +944,16 @@ extern "C" int extrack_predict(extrack_ctx* ctx, const extrack_model* m, int32_t
         if (e != hipSuccess) rc = xt_fail(ctx, EXTRACK_E_HIP, std::string("predict: ") + hipGetErrorString(e));
     }
     return rc;
+}
+
+extern "C" int extrack_predict(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, double* preds)
+{
+    return xt_predict_sync(ctx, m, bucket_id, preds, false);
+}
+
+extern "C" int extrack_predict_gaps(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, double* preds)
+{
+    return xt_predict_sync(ctx, m, bucket_id, preds, true);
 }
 
 // Per-sequence log-probabilities of one bucket in the reference's layout (P_Cs_inter_bound_stats' first return value,

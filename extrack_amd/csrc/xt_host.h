@@ -406,6 +406,7 @@ inline int64_t xt_split_descs(double target, int64_t cap, const std::vector<XtBu
 }
 __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, double* __restrict__ out);
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built
+const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide);  // extrack_gaps.hip: gap-aware instantiations of xt_track_body (wide: more than 256 threads), nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers
 // threshold-fusion plan stage for other translation units (extrack_hip.hip): `cb` gets, per launch group, the kernel arguments with the plan
 // made (a.buckets / a.chunk_end on the device), the track / error dimensionality, the largest group count of its chunks and the longest length

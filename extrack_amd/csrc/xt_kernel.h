@@ -143,7 +143,12 @@ XT_HD XtBucketDesc xt_bind_bucket(const XtKernelArgs& a, int block, int nblocks,
     return d;
 }
 
-template <int G_, int D, int K, bool PREDS, class Ctx>
+// GAPS (compile-time, default off: the instantiations without it are unchanged): a row whose coordinates are ALL NaN is a missed detection
+// at that frame.  The position is integrated out: the step applies the transition / stay factor and the fuse / expand as
+// usual, but no Gaussian factor; the mean stays the fused mean and the stored u becomes d2 + ub (the l2 -> infinity limit of l2*s2/(l2+s2)).
+// The row's per-peak error is never read.  The first and the last row must be observed and a row with only some NaN coordinates is no gap: both
+// poison the track as any NaN does without GAPS.  The per-track constant counts the observed rows: -(n_observed - 1) * D/2 * log(2 pi).
+template <int G_, int D, int K, bool PREDS, bool GAPS = false, class Ctx>
 XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
 {
     int lb, nb;
@@ -170,6 +175,7 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
     double* uu = mm + D * EP;
     int* ze = (int*)(uu + K * EP);
     int* red_e = ze + ((EP + 1) & ~1);  // [2] ints: final-reduce exponent, spare
+    double* ngap = (double*)(red_e + 2);  // GAPS: missed detections of the track, counted where its rows are staged (the region's last double)
     double* pbase = smem + ((ntab + 1) & ~1) + a.TPB * rdoubles + (tvalid ? slot : 0) * xt_pred_doubles(S, F);
     // PREDS accumulators: pe[2] (ints, in one double), pacc[2][S], facc[F+1][S]
     int* pe = (int*)pbase;
@@ -202,6 +208,7 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
     };
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
     if (tvalid && g == 0) red_e[1] = 0;
+    if (GAPS && tvalid && g == 0) *ngap = 0.0;
     cx.sync();
     // compile-time group size: the table rows of this thread's (constant) newest old digit live in registers
     double T0r[G_ ? G_ : 1], T1r[G_ ? G_ : 1], D2r[G_ ? G_ : 1];
@@ -220,6 +227,33 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
 
         // positions [p0, p0 + XT_STAGE) of this track -> LDS, by the track's own threads (coalesced along the track)
         auto stage = [&](int p0) {
+            if (GAPS) {
+                // row by row: all coordinates NaN = a gap (counted; its error is copied but never looked at), some = a NaN input
+                if (act) {
+                    double ng = 0.0;
+                    for (int r = g; r < XT_STAGE; r += NG)
+                        if (p0 + r < L) {
+                            int nn = 0;
+                            for (int d = 0; d < D; ++d) {
+                                const double v = c[(p0 + r) * D + d];
+                                spos[r * D + d] = v;
+                                nn += v != v ? 1 : 0;
+                            }
+                            const bool gap = nn == D;
+                            if ((nn != 0 && !gap) || (gap && (p0 + r == 0 || p0 + r == L - 1))) red_e[1] = 1;
+                            ng += gap ? 1.0 : 0.0;
+                            if (sg)
+                                for (int k = 0; k < a.KS; ++k) {
+                                    const double v = sg[(p0 + r) * a.KS + k];
+                                    ssig[r * a.KS + k] = v;
+                                    if (!gap && v != v) red_e[1] = 1;
+                                }
+                        }
+                    if (ng != 0.0) cx.atomic_add_f64(ngap, ng);
+                }
+                cx.sync();
+                return;
+            }
             if (act) {
                 for (int i = g; i < XT_STAGE * D; i += NG)
                     if (p0 + i / D < L) {
@@ -288,7 +322,8 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
                 const int32_t* off = a.off_tab + ph * G;
                 double ct[D], l2t[K];
                 for (int d = 0; d < D; ++d) ct[d] = spos[(t & (XT_STAGE - 1)) * D + d];
-                load_l2(t, l2t);
+                const bool gap = GAPS && ct[0] != ct[0];  // staged rows are all-NaN or poison the track: the first coordinate decides
+                if (!gap) load_l2(t, l2t);
                 const bool stay = t >= stay_from;
                 const double* TTl = stay ? T1 : T0;
                 auto TT = [&](int q) { return G_ ? (stay ? T1r[G_ ? q : 0] : T0r[G_ ? q : 0]) : TTl[q]; };
@@ -318,7 +353,10 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
                         const int idx = xt_skew(base + off[Q], a.skew);
                         pq[Q].clear();
                         const double zq = zm[idx];
-                        if (zq != 0.0) {
+                        if (gap) {  // no predictive density of a position that was not observed: the transition factor alone
+                            if (zq != 0.0)
+                                for (int q = 0; q < G; ++q) pq[Q].add(zq * TT(q), ze[idx]);
+                        } else if (zq != 0.0) {
                             double dq[D], uq[K], dsq = 0.0;
                             for (int d = 0; d < D; ++d) {
                                 dq[d] = ct[d] - mm[d * EP + idx];
@@ -365,7 +403,16 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
                     dm[d] = ct[d] - mb[d];
                     dsq = xt_fma(dm[d], dm[d], dsq);
                 }
-                for (int q = 0; q < G; ++q) {
+                if (gap) {  // transition-only step (neighbouring lanes of another track may take the other side at the same t: this is the cheap one)
+                    for (int q = 0; q < G; ++q) {
+                        const int idx = xt_skew(base + off[q], a.skew);
+                        zm[idx] = Wm * TT(q);
+                        ze[idx] = We;
+                        for (int d = 0; d < D; ++d) mm[d * EP + idx] = mb[d];
+                        for (int k = 0; k < K; ++k) uu[k * EP + idx] = TDD(q) + ub[k];
+                    }
+                }
+                for (int q = 0; q < (gap ? 0 : G); ++q) {
                     const int idx = xt_skew(base + off[q], a.skew);
                     const double d2 = TDD(q);
                     double quad, gf, tt[K];
@@ -524,7 +571,11 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
         if (act && g == 0) {
             double sum = 0.0;
             for (int i = 0; i < NG; ++i) sum += zm[i];
-            const double ll = poisoned ? NAN : log(sum) + (double)fe * XT_LN2 + b.ll_const;
+            double ll = poisoned ? NAN : log(sum) + (double)fe * XT_LN2 + b.ll_const;
+            if (GAPS) {  // b.ll_const counts every row of the bucket: give back the missed ones' share
+                ll += *ngap * (0.5 * D * XT_LOG2PI);
+                *ngap = 0.0;  // for the next batch (only this thread reads it, and no row is staged before the barrier below)
+            }
             if (b.ll_out) b.ll_out[trk] = ll;
             block_ll += ll;
         }

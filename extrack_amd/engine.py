@@ -103,6 +103,24 @@ def sort_buckets(all_tracks, input_LocErr=None):
     return list(keys), tracks, (sigmas if input_LocErr is not None else None)
 
 
+def check_gap_rows(buckets):
+    """The host-side rules of ``TrackSet(gaps=True)``: in every track the first and the last row are finite and every other row is finite
+    or NaN as a whole.  Raises ValueError naming the first offending bucket (its index in ``buckets``) and track."""
+    for i, b in enumerate(buckets):
+        b = np.asarray(b, dtype=np.float64)
+        if b.ndim != 3 or b.shape[0] == 0 or b.shape[1] < 2:
+            continue  # shape errors are reported by the TrackSet itself
+        nan = np.isnan(b)
+        ok = np.isfinite(b).all(axis=2)
+        bad_end = ~(ok[:, 0] & ok[:, -1])
+        bad_row = ~(ok | nan.all(axis=2)).all(axis=1)
+        bad = bad_end | bad_row
+        if bad.any():
+            n = int(np.argmax(bad))
+            why = "its first and last position must be observed" if bad_end[n] else "a position is finite or NaN in all its coordinates"
+            raise ValueError("gaps=True: bucket %d (length %d), track %d: %s" % (i, b.shape[1], n, why))
+
+
 class TrackSet:
     """Length buckets resident on one GPU.
 
@@ -112,13 +130,20 @@ class TrackSet:
     dataset must be given the global ones (extrack/tracking.py:1009-1010 uses the whole list).
     """
 
-    def __init__(self, buckets, sigmas=None, device=0, min_len=None, max_len=None, allow_empty=False, dts=None):
+    def __init__(self, buckets, sigmas=None, device=0, min_len=None, max_len=None, allow_empty=False, dts=None, gaps=False):
         """allow_empty: a shard of a distributed dataset may hold no track at all (its objective is 0.0, its posteriors are
         empty); the dataset-global ``min_len`` / ``max_len`` must then be given.
         dts: optional list of per-track time steps [N_l, l] matching ``buckets`` (extrack/tracking.py:979-982: ``dt`` given as a
-        dict of arrays); only the threshold-fusion kernels take them."""
+        dict of arrays); only the threshold-fusion kernels take them.
+        gaps: rows whose coordinates are all NaN are missed detections (``extrack_amd.gaps``): a bucket's length is
+        then the frame span of its tracks, the first and the last row of every track must be observed and a row is finite or NaN as a
+        whole (checked here, before anything is uploaded); ``loglik`` / ``predict`` go to the gap-aware kernels.  Without it a NaN
+        poisons its track as before."""
         if len(buckets) < 1 and not allow_empty:
             raise ValueError("No track could be detected. The loaded tracks seem empty. Errors often come from wrong input paths.")
+        self.gaps = bool(gaps)
+        if self.gaps:
+            check_gap_rows(buckets)
         self.ctx = _lib.Context(device)
         self.shapes = []
         self.dt0 = []  # first column of every bucket's dt array (host copy): what the per-chunk field-of-view tables are made from
@@ -190,6 +215,8 @@ class TrackSet:
     def loglik(self, model, per_track=False):
         if not self.shapes:
             return (0.0, np.empty(0)) if per_track else 0.0
+        if self.gaps:
+            return self.ctx.loglik(model, per_track=per_track, gaps=True)
         return self.ctx.loglik(model, per_track=per_track)
 
     def loglik_th(self, model, threshold=0.2, max_nb_states=120, chunk=2000, per_track=False):
@@ -208,6 +235,8 @@ class TrackSet:
 
     def predict(self, model):
         """Posteriors for every uploaded bucket, in upload order: list of arrays [N_l, l, S]."""
+        if self.gaps:
+            return [self.ctx.predict(model, i, gaps=True) for i in range(len(self.shapes))]
         return [self.ctx.predict(model, i) for i in range(len(self.shapes))]
 
     def map_states(self, model, scores=False):

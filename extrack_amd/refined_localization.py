@@ -152,7 +152,8 @@ def refine_along_states(all_tracks, dt, params, states=None, nb_states=2, frame_
 
     Returns ({len: mus [n, len, dims]}, {len: sigs [n, len]}) keyed by every input key - sigs [n, len, dims] with per-dimension errors -
     and with ``return_logdensity`` also {len: float64 [n]}, the log density of each track's displacements given its path (the path's own
-    prior is not part of it).  A track with a NaN position or error, or whose path is -1 (``predict_states`` on such a track), is NaN."""
+    prior is not part of it).  A track with a NaN position or error, or whose path is -1 (``predict_states`` on such a track), is NaN;
+    a missed detection written as a NaN row is such a position here (``gaps`` of ``param_fitting`` / ``predict_Bs`` is not built for the smoother)."""
     from . import tracking
     if not is_parameters(params):
         raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")

@@ -42,3 +42,13 @@ def bucket_sizes_geometric(total, lengths, ratio=0.9):
     n = np.floor(total * w / w.sum()).astype(int)
     n[0] += total - n.sum()
     return {int(l): int(k) for l, k in zip(lengths, n)}
+
+
+def drop_positions(tracks, p_miss, seed=0):
+    """Copy of ``tracks`` [n, length, dims] with interior rows set to NaN independently with probability ``p_miss``: missed detections as
+    ``TrackSet(gaps=True)`` reads them.  The first and the last row of every track are kept."""
+    out = np.array(tracks, dtype=np.float64, copy=True)
+    miss = np.random.default_rng(seed).random(out.shape[:2]) < p_miss
+    miss[:, 0] = miss[:, -1] = False
+    out[miss] = np.nan
+    return out

@@ -346,7 +346,11 @@ def _resolve_device(device, comm):
     return comm.local_device() if comm is not None else 0
 
 
-def _as_trackset(all_tracks, input_LocErr, device=None, comm=None, dt=None):
+_GAPS_NO_THRESHOLD = "missed detections (gaps=True) are built into the fixed-window kernel only: use fusion='window'"
+_GAPS_NO_COMM = "missed detections (gaps=True) are not built for distributed evaluation: fit on one GPU (comm=None)"
+
+
+def _as_trackset(all_tracks, input_LocErr, device=None, comm=None, dt=None, gaps=False):
     """(TrackSet, owned).  A ``TrackSet`` is used as is.  A list of bucket arrays (what the reference's objective receives at
     every call) is uploaded for THIS call only and released afterwards (``owned``): device copies are never cached behind the
     caller's back, so edited or re-allocated arrays can not be confused with earlier ones.  Keep a ``TrackSet`` (or use
@@ -356,8 +360,10 @@ def _as_trackset(all_tracks, input_LocErr, device=None, comm=None, dt=None):
         return all_tracks, False
     dev = _resolve_device(device, comm)
     dts = dt if isinstance(dt, list) else None
+    if gaps and comm is not None:
+        raise NotImplementedError(_GAPS_NO_COMM)
     if comm is None:
-        return TrackSet(list(all_tracks), input_LocErr, device=dev, dts=dts), True
+        return TrackSet(list(all_tracks), input_LocErr, device=dev, dts=dts, gaps=gaps), True
     if dts is not None:
         raise ValueError("per-track time steps with a communicator need chunk-aligned shards: pass the TrackSet of "
                          "Comm.shard_trackset(..., chunk=max_number_of_tracks_per_matrix, dts=...)")
@@ -382,8 +388,10 @@ def _objective_model(params, ts, dt, cell_dims, input_LocErr, nb_states, nb_subs
 
 def cum_Proba_Cs(params, all_tracks, dt, cell_dims, input_LocErr, nb_states, nb_substeps, frame_len, verbose=1, workers=1,
                  Matrix_type=1, threshold=0.2, max_nb_states=120, max_number_of_tracks_per_matrix=2000, comm=None, fusion=None,
-                 device=None):
+                 device=None, gaps=False):
     """-sum of per-track log-likelihoods, or +inf for invalid parameters / NaN (extrack/tracking.py:991-1088).
+    ``gaps``: all-NaN rows of the uploaded bucket arrays are missed detections (``extrack_amd.gaps``; a ``TrackSet`` carries its own
+    flag); fixed-window kernel on one GPU only.
 
     ``all_tracks``: a ``TrackSet`` (device-resident, reused between calls) or the list of bucket arrays sorted short->long that
     the reference passes (uploaded for this call only).  ``comm``: optional extrack_amd.distributed.Comm; ``all_tracks`` is
@@ -394,8 +402,14 @@ def cum_Proba_Cs(params, all_tracks, dt, cell_dims, input_LocErr, nb_states, nb_
     th = _check_fusion(fusion)
     if th and comm is not None and not isinstance(all_tracks, TrackSet):
         raise ValueError("fusion='threshold' with comm needs chunk-aligned shards: pass the TrackSet of comm.shard_trackset(..., chunk=...)")
-    ts, owned = _as_trackset(all_tracks, input_LocErr, device, comm, dt)
+    if gaps and th:
+        raise NotImplementedError(_GAPS_NO_THRESHOLD)
+    ts, owned = _as_trackset(all_tracks, input_LocErr, device, comm, dt, gaps)
     try:
+        if ts.gaps and th:
+            raise NotImplementedError(_GAPS_NO_THRESHOLD)
+        if ts.gaps and comm is not None:
+            raise NotImplementedError(_GAPS_NO_COMM)
         if ts.has_dt and not th:
             raise NotImplementedError("per-track time steps (dt as a dict / list of arrays) exist in the threshold-fusion kernel only "
                                       "(extrack/tracking.py:494-499); the fixed-window kernel of extrack/tracking_0.py has no such input: "
@@ -445,6 +459,8 @@ def cum_Proba_Cs_grad(params, names, all_tracks, dt, cell_dims, input_LocErr, nb
         raise ValueError("fusion='threshold' with comm needs chunk-aligned shards: pass the TrackSet of comm.shard_trackset(..., chunk=...)")
     ts, owned = _as_trackset(all_tracks, input_LocErr, device, comm)
     try:
+        if ts.gaps:
+            raise NotImplementedError("gaps=True: the gradient kernels have no gap-aware variant")
         out, g = gradient.objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, frame_len, Matrix_type, comm, names,
                                                  threshold_fusion=(threshold, max_nb_states, max_number_of_tracks_per_matrix) if th else None)
     finally:
@@ -609,7 +625,7 @@ def _fit_threshold_frozen_plan(params, fargs, method, ts, max_rounds=6):
 # ------------------------------------------------------------------------------------------------------------
 def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame_len=6, verbose=1, workers=1, Matrix_type=1,
                   method="bfgs", steady_state=False, cell_dims=[1], input_LocErr=None, threshold=0.2, max_nb_states=120,
-                  device=None, comm=None, fusion=None, gradient=None, uncertainties=None):
+                  device=None, comm=None, fusion=None, gradient=None, uncertainties=None, gaps=False):
     """Fit the model parameters to a length-bucketed track dict (extrack/tracking.py:1299-1386).
 
     all_tracks: {str(len): ndarray[n_tracks, len, dims]}.  Returns the lmfit (or lmfit_compat) MinimizerResult:
@@ -622,10 +638,22 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     ``uncertainties`` (None / False: point estimates only, as the reference; True or "opg" | "hessian" | "sandwich": after the fit the
     covariance of the free parameters is estimated on the same device-resident tracks - ``extrack_amd.uncertainty`` - and written to
     ``fit.covar``, ``fit.params[name].stderr`` / ``.correl``, ``fit.errorbars``, ``fit.uncertainty_method``, ``fit.uncertainty_message``;
-    fixed-window kernel with a scalar ``dt`` only)."""
+    fixed-window kernel with a scalar ``dt`` only), ``gaps`` (True: rows of ``all_tracks`` whose coordinates are all NaN are missed
+    detections and the bucket keys are frame spans, as ``extrack_amd.gaps.insert_gaps`` makes them; the positions are integrated out
+    exactly, DESIGN.md section 18.  Such fits difference the objective - ``gradient=None`` resolves to "fd" - and are built for
+    fusion="window" on one GPU without ``uncertainties``)."""
     from . import uncertainty
     fusion = "threshold" if _check_fusion(fusion) else "window"
     unc_method = uncertainty.resolve_method(uncertainties)
+    if gaps:
+        if fusion == "threshold":
+            raise NotImplementedError(_GAPS_NO_THRESHOLD)
+        if comm is not None:
+            raise NotImplementedError(_GAPS_NO_COMM)
+        if gradient == "analytic":
+            raise NotImplementedError("gaps=True: the gradient kernels have no gap-aware variant; use gradient=None or 'fd'")
+        if unc_method is not None:
+            raise NotImplementedError("gaps=True: uncertainties need per-track scores, which have no gap-aware kernel")
     if unc_method is not None and (fusion == "threshold" or isinstance(dt, (dict, list))):
         raise NotImplementedError("uncertainties need per-track scores, which the fixed-window kernels with a scalar dt provide: "
                                   "not built for fusion='threshold' or per-track time steps")
@@ -648,7 +676,7 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     if comm is not None:  # per-track time steps are cut like the tracks (whole 2000-track chunks: a chunk's field-of-view table comes from ITS tracks)
         ts = comm.shard_trackset(tracks, sigmas, device=device, chunk=2000 if fusion == "threshold" else None, dts=dts)
     else:
-        ts = TrackSet(tracks, sigmas, device=device, dts=dts)
+        ts = TrackSet(tracks, sigmas, device=device, dts=dts, gaps=gaps)
     from . import lmfit_compat
     can_grad = str(method).lower() in lmfit_compat._GRADIENT_METHODS and not (fusion == "threshold" and dts is not None)
     if gradient not in (None, "analytic", "fd"):
@@ -658,8 +686,10 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     fargs = (ts, dt, cell_dims, sigmas, nb_states, nb_substeps, frame_len, verbose, workers, Matrix_type, threshold, max_nb_states, 2000,
              comm, fusion)
     ginfo = {"gradient_path": "fd", "gradient_why": "requested (gradient='fd')" if gradient == "fd" else "method %r takes no gradient" % method}
+    if gaps and gradient is None:
+        ginfo["gradient_why"] = "gaps=True: the gradient kernels have no gap-aware variant, the objective is differenced"
     try:
-        use_grad = can_grad and gradient != "fd"
+        use_grad = can_grad and gradient != "fd" and not gaps
         if use_grad:
             use_grad = _pick_gradient(params, fargs, explicit=(gradient == "analytic"), comm=comm, info=ginfo)
         if use_grad and fusion == "threshold":
@@ -684,8 +714,10 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
 
 
 def predict_Bs(all_tracks, dt, params, cell_dims=[1], nb_states=4, frame_len=5, max_nb_states=200, threshold=0.1, workers=1,
-               input_LocErr=None, verbose=0, nb_max=1, device=None, comm=None, fusion=None):
+               input_LocErr=None, verbose=0, nb_max=1, device=None, comm=None, fusion=None, gaps=False):
     """Probability of each localisation to be in each state (extrack/tracking.py:792-906).
+    ``gaps``: all-NaN rows are missed detections (``extrack_amd.gaps``); the posterior of the state at such a frame is returned like any
+    other.  Fixed-window kernel on one GPU only.
 
     Returns {str(len): ndarray[n_tracks, len, nb_states]} keyed by every input key (empty arrays for empty
     buckets), rows in input order.  ``nb_substeps`` is forced to 1 like the reference (:839); min/max length
@@ -693,6 +725,10 @@ def predict_Bs(all_tracks, dt, params, cell_dims=[1], nb_states=4, frame_len=5, 
     every bucket on its own GPU and rank 0 gets the row-ordered result (other ranks get None); no collective is needed in
     the data path."""
     fusion = "threshold" if _check_fusion(fusion) else "window"
+    if gaps and fusion == "threshold":
+        raise NotImplementedError(_GAPS_NO_THRESHOLD)
+    if gaps and comm is not None:
+        raise NotImplementedError(_GAPS_NO_COMM)
     device = _resolve_device(device, comm)
     if comm is not None:
         from .distributed import shard_range
@@ -721,7 +757,7 @@ def predict_Bs(all_tracks, dt, params, cell_dims=[1], nb_states=4, frame_len=5, 
     out = {l: np.empty((0, int(l), S)) for l in keys}
     if not tracks:
         return out
-    ts = TrackSet(tracks, sigmas, device=device, min_len=max(int(keys[0]), 2), max_len=int(keys[-1]), dts=dts)
+    ts = TrackSet(tracks, sigmas, device=device, min_len=max(int(keys[0]), 2), max_len=int(keys[-1]), dts=dts, gaps=gaps)
     try:
         if sigmas is not None:
             model = ts.make_model(None, ds, Fs, TrMat, pBL, cell_dims, 1, frame_len, slope_offset=so, dt_chunk=nb_max)
@@ -747,7 +783,7 @@ def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len
     The recursion is that of ``predict_Bs(fusion="window")`` with sums over sequences replaced by selections: exact for tracks of at most
     frame_len + 1 positions, and the most probable survivor of every group of sequences older than frame_len states otherwise.
     ``nb_substeps`` is 1 and min / max length come from all keys, as in ``predict_Bs``.  A track with a NaN position or error gets states
-    -1 and score NaN."""
+    -1 and score NaN - missed detections written as NaN rows included: the ``gaps`` handling of ``predict_Bs`` is not built here."""
     if not is_parameters(params):
         raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")
     if _check_fusion(fusion):

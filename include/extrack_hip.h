@@ -157,6 +157,23 @@ int extrack_sequence_matrix(extrack_ctx* ctx, const extrack_model* model, int32_
  * (predict_Bs forces it, extrack/tracking.py:839). */
 int extrack_predict(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double* preds);
 
+/* Tracks with missed detections: extrack_loglik / extrack_predict with gaps.  A row of a bucket whose coordinates are ALL NaN is a frame
+ * at which the particle was not detected (trackers close such gaps; extrack/readers.py:173-203 returns the frame numbers and nothing
+ * downstream reads them).  The position is integrated out exactly: at such a step the state chain and the diffusion go on - transition
+ * and stay factor, fusion and expansion as at any step - and no observation factor is applied; the variance carried forward is d2 + u.
+ * This is the limit of an infinite localisation error at that row.  The bucket length is the frame span, gaps included: isBL, min_len,
+ * max_len and the stay-in-field-of-view term follow from it as before.  The per-track constant counts the observed rows,
+ * -(n_observed - 1) * dims / 2 * log(2 pi).  The first and the last row of a track must be observed; a NaN first or last row, or a row
+ * with only some NaN coordinates, makes the track's results NaN (as any NaN does in extrack_loglik).  The per-peak error of a gap row
+ * is never read and may be NaN.  Posteriors: the state posterior of the gap position is returned like any other; the predictive
+ * density of a position that was not observed does not weight the posterior of the state leaving the window at that step.
+ * Served by gap-aware instantiations of the general fixed-window kernel (csrc/xt_kernel.h, two states included).  Decided on the
+ * host, nothing is launched, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2, n_states > 4, models whose sequence state does not fit a
+ * workgroup (more than 1024 groups of sequences or more than 160 KiB of LDS per track), buckets with per-track time steps.
+ * extrack_last_kernel_ms / extrack_last_launch_info cover the launches. */
+int extrack_loglik_gaps(extrack_ctx* ctx, const extrack_model* model, double* total_ll, double* per_track);
+int extrack_predict_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double* preds);
+
 /* Most-likely state path of every track of one bucket (windowed Viterbi decoding): states host [n][len] (int8, the state of every
  * position), score host [n] or NULL (log joint density of the track and that path).  Replaces nothing in the reference, which has no
  * such function; it sits beside predict_Bs (extrack/tracking.py:792-906), whose callers segment tracks by the per-position argmax of the
