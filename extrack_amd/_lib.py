@@ -21,7 +21,7 @@ EXPORTS = [
     "extrack_sequence_columns", "extrack_sequence_matrix", "extrack_loglik_th_grad", "extrack_loglik_th_grad_async", "extrack_th_freeze_plan", "extrack_sequence_matrix_th",
     "extrack_multi_create", "extrack_multi_destroy", "extrack_multi_last_error", "extrack_multi_device_count", "extrack_multi_uses_rccl",
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
-    "extrack_loglik_gaps", "extrack_predict_gaps",
+    "extrack_loglik_gaps", "extrack_predict_gaps", "extrack_map_states_gaps", "extrack_refine_fixed_states_gaps",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -106,6 +106,7 @@ def load():
     lib.extrack_loglik_gaps.argtypes = [vp, C.POINTER(ExtrackModel), _dp, vp]
     lib.extrack_predict_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
     lib.extrack_map_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
+    lib.extrack_map_states_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_last_launch_info.argtypes = [vp, C.POINTER(i32 * 6)]
     lib.extrack_p_stay_table.argtypes = [vp, i32, i32, vp, i32, vp]
@@ -121,6 +122,7 @@ def load():
     lib.extrack_refine_positions.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, vp]
     lib.extrack_refine_pos_pdf.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, i64, vp, vp, vp]
     lib.extrack_refine_fixed_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp, vp, vp]
+    lib.extrack_refine_fixed_states_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp, vp, vp]
     lib.extrack_last_grad_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_sequence_columns.argtypes = [i32, i32, i32, i32, i32]
     lib.extrack_sequence_columns.restype = i64
@@ -400,10 +402,11 @@ class Context:
                 [np.ascontiguousarray(cut(stds, k).T)[:, :, None] for k in range(L)],
                 [np.ascontiguousarray(cut(logw, k).T) for k in range(L)])
 
-    def refine_fixed_states(self, model, bucket_id, states, logdens=False):
+    def refine_fixed_states(self, model, bucket_id, states, logdens=False, gaps=False):
         """Positions of one bucket refined along a given state path (extrack_refine_fixed_states): ``states`` int8 [n, len] (a row with a
         negative entry gives NaN outputs) -> posterior means [n, len, dims] and stds [n, len, K] (K = 1, or dims with per-dimension
-        errors), and with ``logdens`` the log density [n] of each track's displacements given its path."""
+        errors), and with ``logdens`` the log density [n] of each track's displacements given its path.  ``gaps``: all-NaN rows are
+        missed detections (extrack_refine_fixed_states_gaps): their positions are interpolated instead of poisoning the track."""
         N, L, D, KS = self.buckets[bucket_id]
         states = np.asarray(states)
         if states.dtype != np.int8 or states.shape != (N, L):
@@ -412,9 +415,9 @@ class Context:
         K = KS if model.c.locerr_mode else int(model.c.locerr_dims)
         mu, sg = np.empty((N, L, D)), np.empty((N, L, K))
         ld = np.empty(N) if logdens else None
-        self._check(self._lib.extrack_refine_fixed_states(self._h, C.byref(model.c), int(bucket_id), states.ctypes.data_as(C.c_void_p),
-                                                          mu.ctypes.data_as(C.c_void_p), sg.ctypes.data_as(C.c_void_p),
-                                                          ld.ctypes.data_as(C.c_void_p) if logdens else None))
+        fn = self._lib.extrack_refine_fixed_states_gaps if gaps else self._lib.extrack_refine_fixed_states
+        self._check(fn(self._h, C.byref(model.c), int(bucket_id), states.ctypes.data_as(C.c_void_p), mu.ctypes.data_as(C.c_void_p),
+                       sg.ctypes.data_as(C.c_void_p), ld.ctypes.data_as(C.c_void_p) if logdens else None))
         return (mu, sg, ld) if logdens else (mu, sg)
 
     def last_grad_ms(self):
@@ -463,14 +466,15 @@ class Context:
         self._check((self._lib.extrack_predict_gaps if gaps else self._lib.extrack_predict)(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def map_states(self, model, bucket_id, scores=False):
+    def map_states(self, model, bucket_id, scores=False, gaps=False):
         """Most-likely state path of every track of one bucket (extrack_map_states): int8 [N, L], and with ``scores`` the log joint
-        density of track and path, float64 [N]."""
+        density of track and path, float64 [N].  ``gaps``: all-NaN rows are missed detections (extrack_map_states_gaps) instead of
+        poisoning their track."""
         N, L, D, KS = self.buckets[bucket_id]
         out = np.empty((N, L), dtype=np.int8)
         sc = np.empty(N) if scores else None
-        self._check(self._lib.extrack_map_states(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p),
-                                                 sc.ctypes.data_as(C.c_void_p) if scores else None))
+        fn = self._lib.extrack_map_states_gaps if gaps else self._lib.extrack_map_states
+        self._check(fn(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p) if scores else None))
         return (out, sc) if scores else out
 
     def sequence_matrix(self, model, bucket_id):

@@ -34,15 +34,19 @@ void xt_cond_release(extrack_ctx* ctx)
     ctx->cond_cap = 0;
 }
 
-extern "C" int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, const int8_t* states, double* mu,
-                                           double* sigma, double* logdens)
+// The launch path of extrack_refine_fixed_states and of extrack_refine_fixed_states_gaps (extrack_cond_gaps.hip): the two differ in the
+// kernel alone.
+int xt_refine_fixed_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, const int8_t* states, double* mu, double* sigma,
+                                  double* logdens, bool gaps)
 {
     if (!ctx || !states || !mu || !sigma) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (bucket_id < 0 || bucket_id >= (int)ctx->buckets.size()) return xt_fail(ctx, EXTRACK_E_INVALID, "bucket id out of range");
     // everything below is decided on the host, before any device work
-    if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_INVALID, "refinement along a state path requires nb_substeps == 1");
+    // (the gap-aware entry point refuses sub-steps as extrack_loglik_gaps does: not built, rather than an invalid model)
+    if (m->nb_substeps != 1)
+        return xt_fail(ctx, gaps ? EXTRACK_E_UNSUPPORTED : EXTRACK_E_INVALID, "refinement along a state path requires nb_substeps == 1");
     const int S = m->n_states;
     if (S < 2 || S > XT_MAX_STATES) return xt_fail(ctx, EXTRACK_E_INVALID, "n_states must be in [2, 8]");
     XtBucket& b = ctx->buckets[bucket_id];
@@ -70,7 +74,7 @@ extern "C" int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model
     const int tpb = 64;
     const size_t lds = xt_cond_lds_doubles(S, L, D, K, tpb, ws_global) * sizeof(double);
     const int threads = tpb;
-    const void* kp = xt_cond_kernel_ptr(D, K, ws_global);
+    const void* kp = gaps ? xt_cond_gap_kernel_ptr(D, K, ws_global) : xt_cond_kernel_ptr(D, K, ws_global);
     if (!kp) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "fixed-state refinement kernel variant not built");
 
     XtCondArgs a;
@@ -149,4 +153,10 @@ extern "C" int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model
     ctx->launch_info[4] = occ;
     ctx->launch_info[5] = ctx->n_cu;
     return EXTRACK_OK;
+}
+
+extern "C" int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, const int8_t* states, double* mu,
+                                           double* sigma, double* logdens)
+{
+    return xt_refine_fixed_states_launch(ctx, m, bucket_id, states, mu, sigma, logdens, false);
 }

@@ -76,13 +76,15 @@ static void xt_map_geometry(const XtConfig& c, int D, int K, int L, int bpw, boo
     lds = fixed + per_track * tpb;
 }
 
-extern "C" int extrack_map_states(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, int8_t* states, double* score)
+// The launch path of extrack_map_states and of extrack_map_states_gaps (extrack_map_gaps.hip): the two differ in the kernel alone.
+int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, int8_t* states, double* score, bool gaps)
 {
     if (!ctx || !states) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (bucket_id < 0 || bucket_id >= (int)ctx->buckets.size()) return xt_fail(ctx, EXTRACK_E_INVALID, "bucket id out of range");
-    if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_INVALID, "state paths require nb_substeps == 1");
+    // (the gap-aware entry point refuses sub-steps as extrack_loglik_gaps does: not built, rather than an invalid model)
+    if (m->nb_substeps != 1) return xt_fail(ctx, gaps ? EXTRACK_E_UNSUPPORTED : EXTRACK_E_INVALID, "state paths require nb_substeps == 1");
     const int S = m->n_states, F = m->frame_len;
     if (S < 2 || F < 2) return xt_fail(ctx, EXTRACK_E_INVALID, "n_states and frame_len must be >= 2");
     // everything below is decided on the host, before any device work
@@ -121,7 +123,7 @@ extern "C" int extrack_map_states(extrack_ctx* ctx, const extrack_model* m, int3
     const int tpb = bp_lds ? tpb_l : tpb_g;
     const size_t lds = bp_lds ? lds_l : lds_g;
     const int threads = (tpb * cgeo.NG + 63) / 64 * 64;
-    const void* kp = xt_map_kernel_ptr(S, D, K, threads);
+    const void* kp = gaps ? xt_map_gap_kernel_ptr(S, D, K, threads) : xt_map_kernel_ptr(S, D, K, threads);
     if (!kp || threads > 1024) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "state-path kernel variant not built");
 
     XT_HIP(ctx, hipSetDevice(ctx->device));
@@ -199,4 +201,9 @@ extern "C" int extrack_map_states(extrack_ctx* ctx, const extrack_model* m, int3
     ctx->launch_info[4] = occ;
     ctx->launch_info[5] = ctx->n_cu;
     return EXTRACK_OK;
+}
+
+extern "C" int extrack_map_states(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, int8_t* states, double* score)
+{
+    return xt_map_states_launch(ctx, m, bucket_id, states, score, false);
 }

@@ -22,6 +22,13 @@
 //   * global (rows of 64 tracks beyond the LDS of a CU): each lane reads its own rows of the inputs and uses its own rows of the OUTPUT
 //     arrays mu / sigma as the workspace between the sweeps - nothing is allocated for it.
 // Both run the same operations in the same order on the same values: the results are bit-identical.
+//
+// GAPS (compile-time, default off: the instantiations without it are unchanged; DESIGN.md sections 18 and 19): a row whose coordinates are
+// all NaN is a missed detection, an observation of infinite error.  The forward sweep predicts through it - p = a[t-1] + q[t-1], f[t] =
+// f[t-1], a[t] = p, nothing added to the log density - without reading its position or its error (the error slot of the row, which may
+// hold NaN, is overwritten by a[t] as at any row); the backward sweep is unchanged and returns the interpolated posterior at the row.  The
+// first and the last row must be observed and a row with only some NaN coordinates is no gap: both poison the track.  The constant of the
+// log density counts the observed rows: -(n_observed - 1) * D/2 * log(2 pi).
 #pragma once
 #include <stddef.h>
 
@@ -68,7 +75,7 @@ __device__ __forceinline__ const double* xt_cond_d2_ptr(const XtCondArgs&)
 inline const double* xt_cond_d2_ptr(const XtCondArgs& a) { return a.d2; }
 #endif
 
-template <int D, int K, bool WS_GLOBAL, class Ctx>
+template <int D, int K, bool WS_GLOBAL, bool GAPS = false, class Ctx>
 XT_HD void xt_cond_body(const XtCondArgs& a, Ctx& cx)
 {
     static_assert(K == 1 || K == D, "one error channel, or one per dimension");
@@ -179,10 +186,28 @@ XT_HD void xt_cond_body(const XtCondArgs& a, Ctx& cx)
             for (int k = 0; k < K; ++k) pa[k] = av[k];
             double quad = 0.0, lm = 1.0;  // sum of r^2 / w;  prod of w = lm * 2^le
             int le = 0;
+            int ngap = 0;  // GAPS: missed detections of the track
             for (int t = 1; t < L; ++t) {
                 const int bc = state_at(t);
                 const double q = d2[bp * S + bc];
                 bp = bc;
+                if (GAPS) {
+                    int nn = 0;
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) nn += pc[t * D + d] != pc[t * D + d] ? 1 : 0;
+                    if (nn == D) {  // a missed detection: predict through it (some NaN coordinates: no gap, the row poisons the track below)
+                        bad = bad || t == L - 1;
+                        ++ngap;
+                        XT_UNROLL
+                        for (int k = 0; k < K; ++k) {
+                            av[k] = av[k] + q;
+                            pa[t * K + k] = av[k];
+                        }
+                        XT_UNROLL
+                        for (int d = 0; d < D; ++d) pf[t * D + d] = f[d];
+                        continue;
+                    }
+                }
                 double l2[K], g[K], rw[K];
                 l2_at(t, l2);
                 XT_UNROLL
@@ -239,7 +264,7 @@ XT_HD void xt_cond_body(const XtCondArgs& a, Ctx& cx)
             }
             if (a.logdens) {
                 const double logw = log(lm) + (double)le * XT_LN2;  // sum over steps and channels of log w
-                a.logdens[trk] = bad ? NAN : -0.5 * ((K == 1 ? (double)D : 1.0) * logw + quad) - (double)(L - 1) * D * 0.5 * XT_LOG2PI;
+                a.logdens[trk] = bad ? NAN : -0.5 * ((K == 1 ? (double)D : 1.0) * logw + quad) - (double)(GAPS ? L - 1 - ngap : L - 1) * D * 0.5 * XT_LOG2PI;
             }
         }
 

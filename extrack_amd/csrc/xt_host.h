@@ -148,6 +148,10 @@ struct DevCtx {
     {
         __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
+    __device__ __forceinline__ void atomic_add_i32(int* p, int v)
+    {
+        __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     __device__ __forceinline__ void atomic_or_u32(uint32_t* p, uint32_t v)
     {
         __hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -417,4 +421,10 @@ void xt_grad_reduce_launch(hipStream_t st, const double* partials, int nrows, in
 void xt_rev_project(hipStream_t st, const double* adj, const double* dblob, int TB, int n_dir, double* out);  // out[i] = <adj, dblob[i]>
 void xt_map_release(extrack_ctx* ctx);  // extrack_map.hip: frees the decoder's scratch and output buffers (extrack_clear_buckets, extrack_destroy)
 void xt_cond_release(extrack_ctx* ctx);  // extrack_cond.hip: frees the smoother's input / output buffer (same callers)
+const void* xt_map_gap_kernel_ptr(int S, int D, int K, int threads);  // extrack_map_gaps.hip: gap-aware instantiations of xt_map_body, nullptr = not built
+const void* xt_cond_gap_kernel_ptr(int D, int K, bool ws_global);  // extrack_cond_gaps.hip: gap-aware instantiations of xt_cond_body, nullptr = not built
+// the launch paths of extrack_map_states / extrack_refine_fixed_states (extrack_map.hip, extrack_cond.hip), shared with their gap-aware twins
+int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, int8_t* states, double* score, bool gaps);
+int xt_refine_fixed_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, const int8_t* states, double* mu, double* sigma,
+                                  double* logdens, bool gaps);
 const void* xt_gradr_kernel_ptr(int G, int D, int K, int NPC);  // extrack_gradr.hip: register-resident gradient kernels (xt_gradr.h), NPC = 3 | 4

@@ -11,6 +11,11 @@
 //   * the states older than the window follow from the back-pointers, newest to oldest.
 // For a track of at most frame_len + 1 positions nothing is ever merged and the path is the exact MAP sequence.
 //
+// GAPS (compile-time, default off: the instantiations without it are unchanged; the definition of xt_kernel.h and DESIGN.md section 18): a
+// row whose coordinates are all NaN is a missed detection.  Its step selects and records its back-pointer as any other, the expand applies
+// the transition / stay factor alone, the mean stays the selected member's and the stored u becomes d2 + u_selected; the state at the row
+// is decoded like any other.  The score's constant counts the observed rows.
+//
 // Organisation: that of xt_track_body - one thread per group, the S^F live sequences of a track in LDS, staged positions, the bucket
 // descriptor table.  Thread g is group g at every step (only the storage slots rotate), so the thread packs its own back-pointers, 2 bits
 // each, into a register word and stores one 32-bit word per 16 steps: word w of group g at bp[w * NG + g], in LDS beside the state or in a
@@ -69,7 +74,7 @@ XT_HD int xt_map_ref_index(const XtKernelArgs& a, int Q, int g, int q)
     return Q * a.pw[F] + rev * S + q;
 }
 
-template <int G_, int D, int K, class Ctx>
+template <int G_, int D, int K, bool GAPS = false, class Ctx>
 XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
 {
     static_assert(G_ >= 2 && G_ <= 4, "2-bit back-pointers");
@@ -104,7 +109,7 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
     double* mm = zm + EP;
     double* uu = mm + D * EP;
     int* ze = (int*)(uu + K * EP);
-    int* red_e = ze + ((EP + 1) & ~1);  // [2] ints: spare, NaN-input flag
+    int* red_e = ze + ((EP + 1) & ~1);  // [2] ints: spare (GAPS: missed detections of the track, counted where its rows are staged), NaN-input flag
     double* spos = smem + ((ntab + 1) & ~1) + a.TPB * rdoubles + sl * xt_stage_doubles(D);
     double* ssig = spos + XT_STAGE * D;
     double* rows0 = smem + ((ntab + 1) & ~1) + a.TPB * (rdoubles + xt_stage_doubles(D));
@@ -120,6 +125,7 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
 
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
     if (tvalid && g == 0) red_e[1] = 0;
+    if (GAPS && tvalid && g == 0) red_e[0] = 0;
     cx.sync();
     double T0r[G], T1r[G], D2r[G];
     for (int q = 0; q < G; ++q) {
@@ -135,6 +141,33 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
         const double* sg = b.sigma ? b.sigma + (act ? trk : 0) * (int64_t)L * a.KS : nullptr;
 
         auto stage = [&](int p0) {
+            if constexpr (GAPS) {  // (discarded otherwise: the contexts of the plain body need no atomic_add_i32)
+                // row by row (as xt_track_body): all coordinates NaN = a gap (counted; its error is copied but never looked at), some = a NaN input
+                if (act) {
+                    int ng = 0;
+                    for (int r = g; r < XT_STAGE; r += NG)
+                        if (p0 + r < L) {
+                            int nn = 0;
+                            for (int d = 0; d < D; ++d) {
+                                const double v = c[(p0 + r) * D + d];
+                                spos[r * D + d] = v;
+                                nn += v != v ? 1 : 0;
+                            }
+                            const bool gap = nn == D;
+                            if ((nn != 0 && !gap) || (gap && (p0 + r == 0 || p0 + r == L - 1))) red_e[1] = 1;
+                            ng += gap ? 1 : 0;
+                            if (sg)
+                                for (int k = 0; k < a.KS; ++k) {
+                                    const double v = sg[(p0 + r) * a.KS + k];
+                                    ssig[r * a.KS + k] = v;
+                                    if (!gap && v != v) red_e[1] = 1;
+                                }
+                        }
+                    if (ng != 0) cx.atomic_add_i32(&red_e[0], ng);
+                }
+                cx.sync();
+                return;
+            }
             if (act) {
                 for (int i = g; i < XT_STAGE * D; i += NG)
                     if (p0 + i / D < L) {
@@ -194,7 +227,8 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
                 const int32_t* off = a.off_tab + ph * G;
                 double ct[D], l2t[K];
                 for (int d = 0; d < D; ++d) ct[d] = spos[(t & (XT_STAGE - 1)) * D + d];
-                load_l2(t, l2t);
+                const bool gap = GAPS && ct[0] != ct[0];  // staged rows are all-NaN or poison the track: the first coordinate decides
+                if (!gap) load_l2(t, l2t);
                 const bool stay = t >= stay_from;
 
                 int emax = XT_EMIN;
@@ -233,7 +267,16 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
                     dm[d] = ct[d] - mb[d];
                     dsq = xt_fma(dm[d], dm[d], dsq);
                 }
-                for (int q = 0; q < G; ++q) {
+                if (gap) {  // transition-only step (a branch: lanes of a neighbouring track may take the other side at the same t, this is the cheap one)
+                    for (int q = 0; q < G; ++q) {
+                        const int idx = xt_skew(base + off[q], a.skew);
+                        zm[idx] = Wm * (stay ? T1r[q] : T0r[q]);
+                        ze[idx] = We;
+                        for (int d = 0; d < D; ++d) mm[d * EP + idx] = mb[d];
+                        for (int k = 0; k < K; ++k) uu[k * EP + idx] = D2r[q] + ub[k];
+                    }
+                }
+                for (int q = 0; q < (gap ? 0 : G); ++q) {
                     const int idx = xt_skew(base + off[q], a.skew);
                     const double d2 = D2r[q];
                     double quad, gf, tt[K];
@@ -377,7 +420,15 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
             int be, bg, bc;
             scan(0, NG, NG > XT_MAP_SCAN ? XT_MAP_SCAN : 1, bm, be, bg, bc);
             const bool ok = !poisoned && bm > 0.0;
-            if (o.score) o.score[trk] = poisoned ? NAN : (bm > 0.0 ? log(bm) + (double)be * XT_LN2 + b.ll_const : -INFINITY);
+            double llc = b.ll_const;
+            if (GAPS) {  // b.ll_const counts every row of the bucket: give back the missed ones' share
+                llc += (double)red_e[0] * (0.5 * D * XT_LOG2PI);
+                // for the next batch: only this thread reads the two, and no row is staged before the barriers below (the plain body clears
+                // its flag after them, where a wavefront of the track that is already staging the next batch can set it first)
+                red_e[0] = 0;
+                red_e[1] = 0;
+            }
+            if (o.score) o.score[trk] = poisoned ? NAN : (bm > 0.0 ? log(bm) + (double)be * XT_LN2 + llc : -INFINITY);
             if (!ok) {
                 for (int i = 0; i < L; ++i) row[i] = -1;
             } else {
@@ -400,6 +451,6 @@ XT_HD void xt_map_body(const XtKernelArgs& a, const XtMapArgs& ma, Ctx& cx)
         if (act)
             for (int i = g; i < L; i += NG) o.states[trk * L + i] = row[i];
         cx.sync();  // the row, the candidates and the back-pointer words are re-used by the next batch
-        if (act && g == 0) red_e[1] = 0;
+        if (!GAPS && act && g == 0) red_e[1] = 0;
     }
 }

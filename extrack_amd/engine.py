@@ -137,7 +137,8 @@ class TrackSet:
         dict of arrays); only the threshold-fusion kernels take them.
         gaps: rows whose coordinates are all NaN are missed detections (``extrack_amd.gaps``): a bucket's length is
         then the frame span of its tracks, the first and the last row of every track must be observed and a row is finite or NaN as a
-        whole (checked here, before anything is uploaded); ``loglik`` / ``predict`` go to the gap-aware kernels.  Without it a NaN
+        whole (checked here, before anything is uploaded); ``loglik`` / ``predict`` / ``map_states`` / ``refine_fixed_states`` go to the
+        gap-aware kernels.  Without it a NaN
         poisons its track as before."""
         if len(buckets) < 1 and not allow_empty:
             raise ValueError("No track could be detected. The loaded tracks seem empty. Errors often come from wrong input paths.")
@@ -242,6 +243,8 @@ class TrackSet:
     def map_states(self, model, scores=False):
         """Most-likely state path for every uploaded bucket, in upload order: list of int8 arrays [N_l, l]; with ``scores`` a list of
         (states, float64 [N_l] log joint density of track and path)."""
+        if self.gaps:
+            return [self.ctx.map_states(model, i, scores=scores, gaps=True) for i in range(len(self.shapes))]
         return [self.ctx.map_states(model, i, scores=scores) for i in range(len(self.shapes))]
 
     def refine_fixed_states(self, model, states_per_bucket, logdens=False):
@@ -250,6 +253,8 @@ class TrackSet:
         (means, stds, log density [N_l] of the track's displacements given its path)."""
         if len(states_per_bucket) != len(self.shapes):
             raise ValueError("one state array per uploaded bucket is required")
+        if self.gaps:
+            return [self.ctx.refine_fixed_states(model, i, st, logdens=logdens, gaps=True) for i, st in enumerate(states_per_bucket)]
         return [self.ctx.refine_fixed_states(model, i, st, logdens=logdens) for i, st in enumerate(states_per_bucket)]
 
     def close(self):

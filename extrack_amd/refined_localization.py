@@ -143,7 +143,7 @@ def get_pos_PDF_fixedBs(Cs, LocErr, ds, Fs, TrMat, Bs, device=0):
 
 
 def refine_along_states(all_tracks, dt, params, states=None, nb_states=2, frame_len=6, cell_dims=[1], input_LocErr=None,
-                        return_logdensity=False, device=0):
+                        return_logdensity=False, device=0, gaps=False):
     """Positions of a whole dataset refined along one state path per track.  ``all_tracks``: {str(len): ndarray[n_tracks, len, dims]};
     ``params``: lmfit-style parameters as for ``predict_states``; ``states``: {str(len): int8 ndarray[n_tracks, len]}, exactly what
     ``tracking.predict_states`` returns, or None to decode the most-likely paths with it first (``nb_states``, ``frame_len``,
@@ -153,7 +153,13 @@ def refine_along_states(all_tracks, dt, params, states=None, nb_states=2, frame_
     Returns ({len: mus [n, len, dims]}, {len: sigs [n, len]}) keyed by every input key - sigs [n, len, dims] with per-dimension errors -
     and with ``return_logdensity`` also {len: float64 [n]}, the log density of each track's displacements given its path (the path's own
     prior is not part of it).  A track with a NaN position or error, or whose path is -1 (``predict_states`` on such a track), is NaN;
-    a missed detection written as a NaN row is such a position here (``gaps`` of ``param_fitting`` / ``predict_Bs`` is not built for the smoother)."""
+    without ``gaps`` a missed detection written as a NaN row is such a position.
+
+    ``gaps``: all-NaN rows are missed detections (``extrack_amd.gaps.insert_gaps``, DESIGN.md sections 18 and 19), checked on the host by
+    the rules of ``TrackSet(gaps=True)`` (ValueError naming bucket and track, before any device call).  mus / sigs at such a row are the
+    posterior mean and standard deviation of where the particle was at the frame it was not detected; the log density is that of the
+    displacements between consecutive observed positions.  ``states`` carry one state per row, missed frames included, as
+    ``predict_states(..., gaps=True)`` returns them; with ``states=None`` the paths are decoded with gaps first."""
     from . import tracking
     if not is_parameters(params):
         raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")
@@ -184,13 +190,13 @@ def refine_along_states(all_tracks, dt, params, states=None, nb_states=2, frame_
         states = {str(k): _check_states(v, shapes[str(k)][0], shapes[str(k)][1], S, "states[%r]" % k) for k, v in states.items()}
     else:
         states = tracking.predict_states(all_tracks, dt, params, cell_dims=cell_dims, nb_states=nb_states, frame_len=frame_len,
-                                         input_LocErr=input_LocErr, device=device)
+                                         input_LocErr=input_LocErr, device=device, gaps=gaps)
     keys, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
     ds = np.sqrt(2 * Ds * dt)
     K = None
     mus, sigs, lds = {}, {}, {l: np.empty(0) for l in keys}
     if tracks:
-        ts = TrackSet(tracks, sigmas, device=device, min_len=max(int(keys[0]), 2), max_len=int(keys[-1]))
+        ts = TrackSet(tracks, sigmas, device=device, min_len=max(int(keys[0]), 2), max_len=int(keys[-1]), gaps=gaps)
         try:
             if sigmas is not None:
                 model = ts.make_model(None, ds, Fs, TrMat, pBL, cell_dims, 1, frame_len, slope_offset=so)

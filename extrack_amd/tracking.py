@@ -774,7 +774,7 @@ def predict_Bs(all_tracks, dt, params, cell_dims=[1], nb_states=4, frame_len=5, 
 
 
 def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len=6, input_LocErr=None, return_scores=False, device=None,
-                   fusion="window"):
+                   fusion="window", gaps=False):
     """Most-likely sequence of states of every track (windowed Viterbi decoding; the reference has no such function - its users take the
     per-position argmax of ``predict_Bs``, extrack/tracking.py:792-906, which is no sequence the model scored as a whole).
 
@@ -783,11 +783,18 @@ def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len
     The recursion is that of ``predict_Bs(fusion="window")`` with sums over sequences replaced by selections: exact for tracks of at most
     frame_len + 1 positions, and the most probable survivor of every group of sequences older than frame_len states otherwise.
     ``nb_substeps`` is 1 and min / max length come from all keys, as in ``predict_Bs``.  A track with a NaN position or error gets states
-    -1 and score NaN - missed detections written as NaN rows included: the ``gaps`` handling of ``predict_Bs`` is not built here."""
+    -1 and score NaN - without ``gaps``, missed detections written as NaN rows included.
+
+    ``gaps``: all-NaN rows are missed detections (``extrack_amd.gaps.insert_gaps``, DESIGN.md sections 18 and 19) and the bucket keys are
+    frame spans; the rules of ``TrackSet(gaps=True)`` are checked on the host (ValueError naming bucket and track, before any device call).
+    The state at a missed frame is decoded like any other, and the score is the log joint density of the OBSERVED positions and the path.
+    Inside a run of two or more consecutive missed frames the density of a path depends on how many frames of the run each state
+    occupies and on the transitions, not on where inside the run an excursion sits: distinct paths tie exactly, the decoder's tie rule
+    (the lowest state) picks one, and the states returned inside such a run are one representative of an equivalence class."""
     if not is_parameters(params):
         raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")
     if _check_fusion(fusion):
-        raise NotImplementedError("predict_states decodes the fixed-window recursion only: use fusion='window'")
+        raise NotImplementedError(_GAPS_NO_THRESHOLD if gaps else "predict_states decodes the fixed-window recursion only: use fusion='window'")
     if isinstance(dt, dict):
         raise NotImplementedError("predict_states is not built for per-track time steps (dt as a dict of arrays)")
     keys, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
@@ -796,7 +803,7 @@ def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len
     states = {l: np.empty((0, int(l)), dtype=np.int8) for l in keys}
     scores = {l: np.empty(0) for l in keys}
     if tracks:
-        ts = TrackSet(tracks, sigmas, device=_resolve_device(device, None), min_len=max(int(keys[0]), 2), max_len=int(keys[-1]))
+        ts = TrackSet(tracks, sigmas, device=_resolve_device(device, None), min_len=max(int(keys[0]), 2), max_len=int(keys[-1]), gaps=gaps)
         try:
             if sigmas is not None:
                 model = ts.make_model(None, ds, Fs, TrMat, pBL, cell_dims, 1, frame_len, slope_offset=so)

@@ -42,6 +42,9 @@
  *       were written to compute: mean and std of every real position given ONE state per position.  Not that function's numbers, which
  *       are inconsistent as shipped: it hands standard deviations to the variance-based integrals it imports from tracking_0 (:27) and
  *       squares their results again (:446, :460, :471), pairs all_Km1[-k] with all_Ks1[-1-k] (:505-506) and reads track 0 only (:478-480).
+ *   extrack_map_states_gaps / extrack_refine_fixed_states_gaps
+ *       the two above for tracks with missed detections (all-NaN rows), as extrack_loglik_gaps / extrack_predict_gaps: nothing in the
+ *       reference, which never reads the frame numbers its readers return (extrack/readers.py:173-203).
  *   extrack_loglik_grad
  *       extrack_loglik AND its exact gradient in one pass.  It replaces the finite-difference loop that the reference's
  *       optimiser runs around cum_Proba_Cs (lmfit.minimize at extrack/tracking.py:1371: BFGS evaluates the objective
@@ -186,6 +189,16 @@ int extrack_predict_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t b
  * with per-track time steps.  extrack_last_kernel_ms covers the launch. */
 int extrack_map_states(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int8_t* states, double* score);
 
+/* extrack_map_states for tracks with missed detections (all-NaN rows, as extrack_loglik_gaps defines them): at such a row the select
+ * and its recorded choice are those of any step, the expand applies the transition / stay factor alone, and the state at the row is
+ * decoded like any other.  score: log joint density of the OBSERVED positions and the path, constant -(n_observed - 1) * dims / 2 *
+ * log(2 pi).  A NaN first or last row, a row with only some NaN coordinates, or a NaN error at an observed row gives states -1 and score
+ * NaN; the per-peak error of a gap row is never read.  Inside a run of two or more consecutive gap rows distinct paths can have exactly
+ * the same density (it depends on how many rows of the run each state occupies, not on where): the tie rule of extrack_map_states
+ * picks one.  Same launch path, back-pointer placement, scratch and refusals as extrack_map_states, except that nb_substeps != 1 is
+ * EXTRACK_E_UNSUPPORTED here (as in extrack_loglik_gaps); gap-free data gives the same bits. */
+int extrack_map_states_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int8_t* states, double* score);
+
 /* Tangent of a model along one direction theta: d(field)/d(theta) for every differentiable field of extrack_model.
  * The diffusion lengths enter as the derivative of their SQUARES (ds^2 = 2 D dt is what the recursion uses, and it keeps the
  * derivative finite at D = 0).  p_stay is a function of ds and cell_dims computed by the caller (extrack_p_stay_table), so its
@@ -313,6 +326,16 @@ int extrack_refine_pos_pdf(extrack_ctx* ctx, const extrack_model* model, int32_t
  * the same bits.  extrack_last_kernel_ms and extrack_last_launch_info cover the launch. */
 int extrack_refine_fixed_states(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, const int8_t* states, double* mu,
                                 double* sigma, double* logdens);
+
+/* extrack_refine_fixed_states for tracks with missed detections (all-NaN rows, as extrack_loglik_gaps defines them): such a row is an
+ * observation of infinite error.  mu / sigma at the row are the interpolated posterior of the real position there (given the states of
+ * the row and its neighbours, as everywhere); logdens is the log density of the displacements between consecutive OBSERVED positions
+ * given the path, constant -(n_observed - 1) * dims / 2 * log(2 pi).  The position and the per-peak error of a gap row are never read.
+ * NaN in all three outputs: a NaN first or last row, a row with only some NaN coordinates, a NaN error at an observed row, a negative
+ * state anywhere (gap rows included).  Same launch path, placements and refusals as extrack_refine_fixed_states, except that
+ * nb_substeps != 1 is EXTRACK_E_UNSUPPORTED here (as in extrack_loglik_gaps); gap-free data gives the same bits. */
+int extrack_refine_fixed_states_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, const int8_t* states, double* mu,
+                                     double* sigma, double* logdens);
 
 /* Threshold-fusion log-likelihood (the kernel extrack.tracking.param_fitting / cum_Proba_Cs call in v1.6.3,
  * extrack/tracking.py:427-743).  Which state sequences are merged at a step is decided from the first 30 tracks
