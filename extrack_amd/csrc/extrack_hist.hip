@@ -53,13 +53,8 @@ extern "C" int extrack_segment_len_hist(extrack_ctx* ctx, const extrack_model* m
     XtBucket& b = ctx->buckets[bucket_id];
     const int D = b.D, L = b.L;
     int K;
-    if (m->locerr_mode == 0) {
-        K = m->locerr_dims;
-        if (K != 1 && K != D) return xt_fail(ctx, EXTRACK_E_INVALID, "locerr_dims must be 1 or the track dimensionality");
-    } else {
-        if (!b.d_sigma) return xt_fail(ctx, EXTRACK_E_INVALID, "per-peak localisation error mode but the bucket has no sigma");
-        K = b.KS;
-    }
+    XtBucket* const bp = &b;
+    if ((rc = xt_th_locerr_dims(ctx, m, &bp, 1, &K))) return rc;
     XtHistArgs a;
     memset(&a, 0, sizeof(a));
     a.bits = S <= 2 ? 1 : (S <= 4 ? 2 : 3);
@@ -104,16 +99,9 @@ extern "C" int extrack_segment_len_hist(extrack_ctx* ctx, const extrack_model* m
     const int grid = (int)std::min<int64_t>(b.N, (int64_t)ctx->n_cu * per_cu * 2);
     a.ws_stride = 2 * (int64_t)xt_hist_parent_doubles(a.PC, D, K, a.HW);
     if (!a.par_lds) {
-        const size_t need = (size_t)a.ws_stride * grid * sizeof(double);
-        if (need > ctx->th_ws_cap) {
-            XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (ctx->d_th_ws) (void)hipFree(ctx->d_th_ws);
-            ctx->d_th_ws = nullptr;
-            ctx->th_ws_cap = 0;
-            XT_HIP(ctx, hipMalloc(&ctx->d_th_ws, need));
-            ctx->th_ws_cap = need;
-        }
-        a.ws = ctx->d_th_ws;
+        extrack_ctx::ThSlot& sl = ctx->th_slot[0];  // the workspace of the threshold-fusion plan kernel, which never runs beside this one
+        if ((rc = xt_grow_device(ctx, (void**)&sl.d_ws, &sl.ws_cap, (size_t)a.ws_stride * grid * sizeof(double), "histogram workspace"))) return rc;
+        a.ws = sl.d_ws;
     }
     const int nbins = (L - 1) * S;
     if ((rc = xt_reserve_partials(ctx, (size_t)grid * nbins + nbins))) return rc;

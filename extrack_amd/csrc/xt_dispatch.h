@@ -81,3 +81,15 @@ static inline bool xt_dispatch_entry(int GP, int D, int K, L& l)
     if (GP == 64) return xt_dispatch_entry_dk<64>(D, K, l);
     return false;
 }
+
+// ---- kernels instantiated over (D, K) alone (threshold fusion, xt_th.h): run_dk<D, K>()
+template <class L>
+static inline bool xt_dispatch_dk(int D, int K, L& l)
+{
+    if (D == 1 && K == 1) return l.template run_dk<1, 1>();
+    if (D == 2 && K == 1) return l.template run_dk<2, 1>();
+    if (D == 2 && K == 2) return l.template run_dk<2, 2>();
+    if (D == 3 && K == 1) return l.template run_dk<3, 1>();
+    if (D == 3 && K == 3) return l.template run_dk<3, 3>();
+    return false;
+}

@@ -1,6 +1,7 @@
-// Host-side state of libextrack_hip.so shared by its translation units (extrack_hip.hip: likelihood / posterior / threshold-fusion
-// entry points; extrack_grad.hip: likelihood + gradient; extrack_hist.hip: state-duration histograms) and the device-side
-// execution context the kernel bodies are written against.
+// Host-side state of libextrack_hip.so shared by its translation units (extrack_hip.hip: context, buckets, fixed-window likelihood /
+// posteriors; extrack_th.hip: threshold-fusion likelihood / posteriors; extrack_refine.hip: position refinement; extrack_grad.hip:
+// likelihood + gradient; extrack_hist.hip: state-duration histograms; ...) and the device-side execution context the kernel bodies are
+// written against.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,6 +20,7 @@
 #include "xt_launch_split.h"
 #include "xt_tables.h"
 #include "xt_th.h"
+#include "xt_th_geom.h"
 
 // ------------------------------------------------------------------------------------------------
 // device side
@@ -276,7 +278,7 @@ struct extrack_ctx {
     double* d_preds = nullptr;      // posterior output buffer, kept between extrack_predict / extrack_predict_th calls
     size_t preds_cap = 0;
     double* d_th_blobs = nullptr;   // threshold-fusion path with per-track time steps: one table blob per chunk
-    size_t th_blobs_cap = 0;        // doubles
+    size_t th_blobs_cap = 0;        // bytes
     double* d_dblob = nullptr;      // gradient path: tangent tables [n_dir][TB]
     size_t dblob_cap = 0;           // doubles
     double* d_dblob2 = nullptr;     // the same blocks in launch order (2-state kernels: full directions first, then the uniform ones)
@@ -300,7 +302,7 @@ struct extrack_ctx {
     size_t opgpart_cap = 0;
     double* d_partials = nullptr;
     size_t partials_cap = 0;
-    static constexpr int RF_SLOTS = 10;   // position refinement: grow-only device buffers kept between calls (extrack_hip.hip: XT_RF_*)
+    static constexpr int RF_SLOTS = 10;   // position refinement: grow-only device buffers kept between calls (extrack_refine.hip: XT_RF_*)
     void* rf_buf[RF_SLOTS] = {nullptr};
     size_t rf_cap_bytes[RF_SLOTS] = {0};
     double* d_total = nullptr;
@@ -318,33 +320,25 @@ struct extrack_ctx {
     bool timed = false;
     int32_t launch_info[6] = {0, 0, 0, 0, 0, 0};
     std::map<std::pair<const void*, std::pair<int, size_t>>, int> occ_cache;
-    double* d_th_ws = nullptr;  // plan-kernel workspace
-    size_t th_ws_cap = 0;
     int th_capE = 128;          // plan capacity (expanded sequences per step); grows on overflow
     int th_learnP = 0, th_learnE = 0;  // live parent / expanded sequence counts seen by the last plan (+ headroom): LDS workspace sizing
     std::vector<int32_t> th_status_host;
-    int32_t* h_th_status = nullptr;  // pinned: plan status of every chunk of a launch group
-    int32_t* d_th_status = nullptr;
-    size_t th_status_cap = 0;        // ints
-    XtThBucket* d_th_desc = nullptr;  // bucket descriptors of a launch group
-    size_t th_desc_cap = 0;
-    int32_t* d_th_cend = nullptr;     // chunk prefix of a launch group
-    size_t th_cend_cap = 0;
-    // more sets of the per-launch buffers above + side streams: several launch groups of one evaluation in flight (xt_th_use_slot)
+    // per-launch buffers of a threshold-fusion launch group (capacities in bytes).  Set 0 serves everything that runs one launch at a time
+    // (single-stream evaluations, extrack_predict_th, refinement, the histogram kernel's workspace); an evaluation that keeps several
+    // launch groups in flight gives segment j set j and side stream j (extrack_th.hip: xt_th_run_split)
     struct ThSlot {
-        int32_t* h_status = nullptr;
+        int32_t* h_status = nullptr;  // pinned: plan status of every chunk of the launch group
         int32_t* d_status = nullptr;
         size_t status_cap = 0;
-        XtThBucket* d_desc = nullptr;
+        XtThBucket* d_desc = nullptr;  // bucket descriptors of the launch group
         size_t desc_cap = 0;
-        int32_t* d_cend = nullptr;
+        int32_t* d_cend = nullptr;     // its chunk prefix
         size_t cend_cap = 0;
-        double* d_ws = nullptr;
+        double* d_ws = nullptr;        // plan-kernel workspace
         size_t ws_cap = 0;
     };
     static constexpr int TH_SLOTS = 3;
-    ThSlot th_slot[TH_SLOTS];   // parked sets; the current one lives in the fields above
-    int th_cur_slot = 0;
+    ThSlot th_slot[TH_SLOTS];
     hipStream_t th_streams[TH_SLOTS] = {nullptr, nullptr, nullptr};
     hipEvent_t th_ev[TH_SLOTS + 1] = {nullptr, nullptr, nullptr, nullptr};
     bool th_split_active = false, th_no_split = false;  // EXTRACK_TH_NO_SPLIT=1: never run several launch groups concurrently
@@ -353,10 +347,7 @@ struct extrack_ctx {
     // (0: no third group), the rest the last (EXTRACK_TH_SPLIT_PCT="hi,lo")
     int th_split_pct[2] = {50, 25};
     float th_plan_ms = 0.f;
-    int th_force_single = 0;
     int th_pair_lanes = 4;  // EXTRACK_TH_PAIR_LANES
-    int th_stage_in_lds_mode = 0;  // EXTRACK_TH_STAGE_LDS: LDS-typed copy of the pilot means/stds also when the state is in LDS (measured: no gain)
-    int th_no_gen_single = 0;  // EXTRACK_TH_NO_GEN_SINGLE: never use the one-buffer general apply variant
     int th_plan_bs = 0;         // plan kernel, > 64 sequences: pivot rows per batch = wavefronts x max(n, 1); < 0: one batch (EXTRACK_TH_PLAN_BS)
     // Frozen plan (extrack_th_freeze_plan): threshold-fusion evaluations skip the plan kernel and follow the plan the last planning
     // evaluation left in the buckets; per launch group (keyed by its first bucket and size) the sequence counts that size the apply / gradient launch
@@ -370,9 +361,10 @@ struct extrack_ctx {
     size_t cond_cap = 0;         // bytes
     bool th_frozen = false;  // the per-bucket sequence counts that size the apply / gradient launch: XtBucket::th_maxG, th_sumE
     std::vector<double> blob_host;  // model tables of the current fixed-window evaluation (xt_prepare)
-    bool th_plan_threads_forced = false;
-    int th_plan_threads = 512;  // workgroup size of the plan kernel (EXTRACK_TH_PLAN_THREADS)
-    int th_force_tt = 0, th_force_threads = 0, th_oversub = 2;  // tuning knobs (EXTRACK_TH_TT / _THREADS / _OVERSUB)
+    // tuning knobs of the threshold-fusion launch geometry (xt_th_geom.h).  stage_in_lds_mode: LDS-typed copy of the pilot means / stds also
+    // when the state is in LDS (measured: no gain); no_gen_single: never use the one-buffer general apply variant; plan_threads: workgroup
+    // size of the plan kernel
+    XtThKnobs th_knobs;
     std::string err;
 };
 
@@ -390,6 +382,10 @@ static const int XT_DESC_CAP = 4096;  // bucket descriptors per evaluation (buck
 
 // shared host helpers (defined in extrack_hip.hip)
 int xt_fail(extrack_ctx* ctx, int code, const std::string& msg);
+// Grow-only device buffer: when `bytes` exceeds *cap, waits for ctx->stream, frees *buf and allocates `alloc` bytes (0: `bytes`); with
+// `pinned`, a pinned host buffer of the same size is kept beside it.  A failed allocation reports "<what>: <HIP error>".
+int xt_grow_device(extrack_ctx* ctx, void** buf, size_t* cap, size_t bytes, const char* what, size_t alloc = 0, void** pinned = nullptr);
+int xt_reserve_preds(extrack_ctx* ctx, size_t bytes);  // posterior output buffer ctx->d_preds of at least `bytes` bytes (kept for the next call)
 int xt_validate_model(extrack_ctx* ctx, const extrack_model* m);
 void xt_model_host(const extrack_model* m, XtModelHost& mh);
 int xt_upload_blob(extrack_ctx* ctx, const std::vector<double>& blob);   // -> ctx->d_blob (double-buffered staging)
@@ -412,10 +408,19 @@ __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, d
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built
 const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide);  // extrack_gaps.hip: gap-aware instantiations of xt_track_body (wide: more than 256 threads), nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers
-// threshold-fusion plan stage for other translation units (extrack_hip.hip): `cb` gets, per launch group, the kernel arguments with the plan
+// threshold-fusion plan stage for other translation units (extrack_th.hip): `cb` gets, per launch group, the kernel arguments with the plan
 // made (a.buckets / a.chunk_end on the device), the track / error dimensionality, the largest group count of its chunks and the longest length
 typedef std::function<int(XtThArgs& a, int D, int K, int maxG, int Lmax)> XtThAfterPlan;
 int xt_th_plan_groups(extrack_ctx* ctx, const extrack_model* m, double threshold, int32_t max_nb_states, int32_t chunk, const XtThAfterPlan& cb);
+// Posterior / recording mode of the plan kernel is launched with 64 or 256 threads per chunk: bounded by 256 threads, PW waves per SIMD asked of
+// the register allocator (the fit-mode plan walks with up to 1024 threads: 128 VGPRs).  Measured r03 (kernel ms; 2 states 2e5 x 30 | 4 states
+// 5e4 x 60, nb_max 1): 3 waves 77.6 | 433, 4 waves 99.0 | 354, 5 waves 93.3 | 382, 6 waves 87.5 | 365, 8 waves 97.2 | 446 -> 3 for two
+// states (168 VGPRs, no spills), else 4.
+static inline int xt_th_pred_waves(int S) { return S == 2 ? 3 : 4; }
+// the prediction-mode plan kernel on ctx->stream (extrack_th.hip instantiates it; extrack_refine.hip records through it)
+hipError_t xt_th_launch_predict(extrack_ctx* ctx, const XtThArgs& a, int D, int K, int grid, int threads, size_t lds);
+// K = dims of the localisation error the kernels see: locerr_dims (one global error) or the buckets' sigma dims (per-peak modes)
+int xt_th_locerr_dims(extrack_ctx* ctx, const extrack_model* m, XtBucket* const* bks, int nbk, int* K);
 // column sums of per-block partials [nrows][ncol] (extrack_grad.hip): column 0 -> *ll_dst, column 1 + i -> out[i]
 void xt_grad_reduce_launch(hipStream_t st, const double* partials, int nrows, int ncol, double* ll_dst, double* out);
 void xt_rev_project(hipStream_t st, const double* adj, const double* dblob, int TB, int n_dir, double* out);  // out[i] = <adj, dblob[i]>

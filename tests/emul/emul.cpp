@@ -27,6 +27,7 @@
 #include "../../extrack_amd/csrc/xt_thgrad2.h"
 #include "../../extrack_amd/csrc/xt_big.h"
 #include "../../extrack_amd/csrc/xt_launch_split.h"
+#include "../../extrack_amd/csrc/xt_th_geom.h"
 
 struct EmulLauncher {
     XtKernelArgs a;
@@ -347,6 +348,24 @@ extern "C" long long xt_emul_split_blocks(double target, long long cap, int nb, 
     std::vector<int64_t> n(N, N + (nb > 0 ? nb : 0));
     std::vector<int32_t> l(L, L + (nb > 0 ? nb : 0));
     return xt_split_blocks(target, cap, nb, n.data(), l.data(), tracks_per_block, (int32_t*)blk_end);
+}
+
+// The launch geometry of the threshold-fusion path (csrc/xt_th_geom.h), as the library compiles it.  in / out: the arguments / result fields in
+// declaration order, kn: the XtThKnobs fields in declaration order.
+static XtThKnobs xt_emul_knobs(const int* kn) { return XtThKnobs{kn[0], kn[1], kn[2], kn[3], kn[4], kn[5], kn[6], kn[7], kn[8]}; }
+extern "C" void xt_emul_th_plan_geom(const long long* in, const int* kn, long long* out)
+{
+    const XtThPlanGeom g = xt_th_plan_geom((int)in[0], (int)in[1], (int)in[2], (int)in[3], (int)in[4], (int)in[5], (int)in[6], (int)in[7], (int)in[8], (int)in[9],
+                                           (int)in[10], (int)in[11], in[12] != 0, xt_emul_knobs(kn));
+    const long long o[12] = {g.grid, (long long)g.lds, g.ws_lds, g.wsP, g.wsE, g.stP, g.stE, g.plan_glb, g.ws_stride, (long long)g.ws_bytes, g.plan_threads, g.fits};
+    for (int i = 0; i < 12; ++i) out[i] = o[i];
+}
+extern "C" void xt_emul_th_apply_geom(const long long* in, const int* kn, long long* out)
+{
+    const XtThApplyGeom g = xt_th_apply_geom((int)in[0], (int)in[1], (int)in[2], (int)in[3], (int)in[4], (int)in[5], (int)in[6], (int)in[7], (int)in[8], (int)in[9],
+                                             (int)in[10], in[11] != 0, (int)in[12], xt_emul_knobs(kn));
+    const long long o[11] = {g.plan_cap, g.TT, g.logTT, g.single_buf, g.mode, g.threads, (long long)g.lds, g.blocks_per_cu, g.bpc, g.grid, g.fits};
+    for (int i = 0; i < 11; ++i) out[i] = o[i];
 }
 
 // Several length buckets served by ONE emulated launch of the global-state body (csrc/xt_big.h), the way xt_launch_group launches it: grid

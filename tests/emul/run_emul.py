@@ -14,7 +14,7 @@ def lib():
         so = os.path.join(HERE, "libxt_emul.so")
         src = os.path.join(HERE, "emul.cpp")
         hdrs = [os.path.join(HERE, "..", "..", "extrack_amd", "csrc", h) for h in ("xt_kernel.h", "xt_math.h", "xt_tables.h", "xt_dispatch.h", "xt_th.h", "xt_entry.h", "xt_fast2.h", "xt_grad.h",
-                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h", "xt_launch_split.h")]
+                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h", "xt_launch_split.h", "xt_th_geom.h")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src, os.path.join(HERE, "emul_r2.cpp"), os.path.join(HERE, "emul_gradr.cpp"), os.path.join(HERE, "emul_rev.cpp"), os.path.join(HERE, "emul_ctx.h")] + hdrs):
             import subprocess
             units = ["emul.cpp", "emul_r2.cpp", "emul_gradr.cpp", "emul_rev.cpp"]  # compiled side by side: emul_r2.cpp unrolls the whole step loop per instance
@@ -111,6 +111,15 @@ def split_blocks(target, cap, Ns, Ls, tracks_per_block):
     g = f(C.c_double(target), C.c_longlong(cap), nb, (C.c_longlong * max(nb, 1))(*Ns), (C.c_int * max(nb, 1))(*Ls), int(tracks_per_block), be)
     end = np.array(be[:nb], np.int64)
     return int(g), np.diff(np.concatenate([[0], end])) if g >= 0 else None
+
+
+def th_geom(which, args, knobs):
+    """The threshold-fusion launch geometry (csrc/xt_th_geom.h): xt_th_plan_geom ("plan": 13 arguments -> 12 result fields) or xt_th_apply_geom
+    ("apply": 13 -> 11), arguments and result fields in declaration order, knobs = the XtThKnobs fields in declaration order."""
+    n_out = 12 if which == "plan" else 11
+    out = (C.c_longlong * n_out)()
+    getattr(lib(), "xt_emul_th_%s_geom" % which)((C.c_longlong * 13)(*[int(v) for v in args]), (C.c_int * 9)(*[int(v) for v in knobs]), out)
+    return list(out)
 
 
 def run_big_multi(buckets, locerr, ds, Fs, T, pBL, p_stay, ns, F, min_len, max_len, target, cap, blocks_per_bucket=None, preds=False):
