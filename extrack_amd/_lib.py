@@ -22,6 +22,7 @@ EXPORTS = [
     "extrack_multi_create", "extrack_multi_destroy", "extrack_multi_last_error", "extrack_multi_device_count", "extrack_multi_uses_rccl",
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
     "extrack_loglik_gaps", "extrack_predict_gaps", "extrack_map_states_gaps", "extrack_refine_fixed_states_gaps",
+    "extrack_loglik_grad_gaps", "extrack_loglik_grad_gaps_async", "extrack_loglik_scores_gaps", "extrack_loglik_scores_gaps_async",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -118,6 +119,10 @@ def load():
     lib.extrack_loglik_grad_async.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), vp]
     lib.extrack_loglik_scores.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), _dp, vp, vp, vp]
     lib.extrack_loglik_scores_async.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.POINTER(ExtrackModelTangent), vp]
+    lib.extrack_loglik_grad_gaps.argtypes = lib.extrack_loglik_grad.argtypes
+    lib.extrack_loglik_grad_gaps_async.argtypes = lib.extrack_loglik_grad_async.argtypes
+    lib.extrack_loglik_scores_gaps.argtypes = lib.extrack_loglik_scores.argtypes
+    lib.extrack_loglik_scores_gaps_async.argtypes = lib.extrack_loglik_scores_async.argtypes
     lib.extrack_segment_len_hist.argtypes = [vp, C.POINTER(ExtrackModel), i32, i32, vp]
     lib.extrack_refine_positions.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, vp]
     lib.extrack_refine_pos_pdf.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, i64, vp, vp, vp]
@@ -307,36 +312,39 @@ class Context:
                 e.ds2, e.Fs, e.TrMat, e.p_stay = [C.cast(b + i * st, _dp) for b, st in zip(base, step)]
         return n, arr, keep
 
-    def loglik_grad(self, model, tangents):
-        """(sum LL, d sum LL / d theta_i) for the model directions ``tangents`` (see ``_pack_tangents``)."""
+    def loglik_grad(self, model, tangents, gaps=False):
+        """(sum LL, d sum LL / d theta_i) for the model directions ``tangents`` (see ``_pack_tangents``).  ``gaps``: all-NaN rows are missed
+        detections (extrack_loglik_grad_gaps: the gap-aware forward-mode kernels) instead of poisoning their track."""
         n, arr, keep = self._pack_tangents(model, tangents)
         tot = C.c_double(0.0)
         g = np.zeros(max(n, 1))
-        self._check(self._lib.extrack_loglik_grad(self._h, C.byref(model.c), n, arr, C.byref(tot), g.ctypes.data_as(C.c_void_p)))
+        self._check((self._lib.extrack_loglik_grad_gaps if gaps else self._lib.extrack_loglik_grad)(self._h, C.byref(model.c), n, arr, C.byref(tot), g.ctypes.data_as(C.c_void_p)))
         return tot.value, g[:n]
 
-    def loglik_grad_async(self, model, tangents, d_out_ptr):
+    def loglik_grad_async(self, model, tangents, d_out_ptr, gaps=False):
         """Enqueues the evaluation on the context's stream; the DEVICE buffer ``d_out_ptr`` (1 + n doubles) receives
-        {sum LL, gradient} in stream order (the multi-GPU objective all-reduces it there)."""
+        {sum LL, gradient} in stream order (the multi-GPU objective all-reduces it there).  ``gaps`` as in ``loglik_grad``."""
         n, arr, keep = self._pack_tangents(model, tangents)
-        self._check(self._lib.extrack_loglik_grad_async(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
+        self._check((self._lib.extrack_loglik_grad_gaps_async if gaps else self._lib.extrack_loglik_grad_async)(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
         return n
 
-    def loglik_scores(self, model, tangents, scores=False):
+    def loglik_scores(self, model, tangents, scores=False, gaps=False):
         """(sum LL, gradient [n], opg [n, n]) and, with ``scores``, the per-track scores [n_tracks, n] (rows: the buckets in upload order,
-        as ``loglik(per_track=True)``) for the model directions ``tangents``: extrack_loglik_scores, forward-mode kernels only."""
+        as ``loglik(per_track=True)``) for the model directions ``tangents``: extrack_loglik_scores, forward-mode kernels only.
+        ``gaps``: all-NaN rows are missed detections (extrack_loglik_scores_gaps)."""
         n, arr, keep = self._pack_tangents(model, tangents)
         tot = C.c_double(0.0)
         g, B = np.zeros(max(n, 1)), np.zeros((max(n, 1), max(n, 1)))
         sc = np.empty((self.n_tracks(), n)) if scores else None
-        self._check(self._lib.extrack_loglik_scores(self._h, C.byref(model.c), n, arr, C.byref(tot), g.ctypes.data_as(C.c_void_p),
-                                                    B.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p) if scores else None))
+        self._check((self._lib.extrack_loglik_scores_gaps if gaps else self._lib.extrack_loglik_scores)(self._h, C.byref(model.c), n, arr, C.byref(tot), g.ctypes.data_as(C.c_void_p),
+            B.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p) if scores else None))
         return (tot.value, g, B, sc) if scores else (tot.value, g, B)
 
-    def loglik_scores_async(self, model, tangents, d_out_ptr):
-        """Enqueues the evaluation; the DEVICE buffer ``d_out_ptr`` (1 + n + n * n doubles) receives {sum LL, gradient, opg} in stream order."""
+    def loglik_scores_async(self, model, tangents, d_out_ptr, gaps=False):
+        """Enqueues the evaluation; the DEVICE buffer ``d_out_ptr`` (1 + n + n * n doubles) receives {sum LL, gradient, opg} in stream order.
+        ``gaps`` as in ``loglik_scores``."""
         n, arr, keep = self._pack_tangents(model, tangents)
-        self._check(self._lib.extrack_loglik_scores_async(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
+        self._check((self._lib.extrack_loglik_scores_gaps_async if gaps else self._lib.extrack_loglik_scores_async)(self._h, C.byref(model.c), n, arr, C.c_void_p(d_out_ptr)))
         return n
 
     def sequence_matrix_th(self, model, bucket_id, threshold=0.2, max_nb_states=120):

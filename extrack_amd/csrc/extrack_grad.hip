@@ -83,6 +83,19 @@ struct GradLauncher {
         if (threads <= 256) return launch(xt_grad_kernel<G_, D, K, 256>);
         return launch(xt_grad_kernel<G_, D, K, 1024>);
     }
+    // the gap-aware instantiations live in extrack_grad_gaps.hip: launched through their address
+    bool run_gaps(int G, int D, int K)
+    {
+        const void* kp = xt_grad_gap_kernel_ptr(G, D, K, threads > 256);
+        if (!kp) return false;
+        if (lds > 64 * 1024) {
+            herr = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (herr != hipSuccess) return true;
+        }
+        void* kargs[2] = {(void*)&a, (void*)&ga};
+        herr = hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream);
+        return true;
+    }
     template <class KernT>
     bool launch(KernT kern)
     {
@@ -125,6 +138,88 @@ static size_t xt_grad_lds_bytes(const XtConfig& c, int D, int K, int NP, int tpb
     return d * sizeof(double);
 }
 
+// Geometry of one pass of the LDS-resident kernel (xt_grad.h) with NP directions
+struct XtGradLdsGeom {
+    bool tan_lds;
+    int PJ, tpb, threads;
+    size_t lds;
+};
+static XtGradLdsGeom xt_grad_lds_geometry(const XtConfig& c, int D, int K, int NP)
+{
+    XtGradLdsGeom o;
+    o.tan_lds = (size_t)NP * xt_grad_tb_doubles(c.S, c.G) * 8 <= 16 * 1024;
+    const size_t per_track = xt_grad_lds_bytes(c, D, K, NP, 1, o.tan_lds) - xt_grad_lds_bytes(c, D, K, NP, 0, o.tan_lds);
+    const size_t fixed = xt_grad_lds_bytes(c, D, K, NP, 0, o.tan_lds);
+    const size_t budget = 64 * 1024;
+    // PJ lanes per group: about two directions per lane, as long as a track's threads fit a workgroup
+    int PJ = 1;
+    while (PJ < 8 && PJ * 2 <= NP && NP > 2 * PJ - 1 && c.NG * PJ * 2 <= 1024) PJ *= 2;
+    if (const char* ev = getenv("EXTRACK_GRAD_PJ")) {
+        const int v = atoi(ev);
+        if ((v == 1 || v == 2 || v == 4 || v == 8) && c.NG * v <= 1024) PJ = v;
+    }
+    const int NT = c.NG * PJ;
+    const int by_threads = NT >= 256 ? 1 : 256 / NT;
+    const int by_lds = budget > fixed + per_track ? (int)((budget - fixed) / per_track) : 1;
+    o.PJ = PJ;
+    o.tpb = std::max(1, std::min(by_threads, by_lds));
+    o.threads = (o.tpb * NT + 63) / 64 * 64;
+    o.lds = xt_grad_lds_bytes(c, D, K, NP, o.tpb, o.tan_lds);
+    return o;
+}
+// directions per pass of the LDS-resident kernel: as many as keep one track's state within the LDS of a CU (all of them for the usual models)
+static int xt_grad_lds_npass_dir(const XtConfig& c, int D, int K, int n_dir)
+{
+    int npass_dir = std::max(n_dir, 1);
+    while (npass_dir > 1 && (npass_dir > 16 || xt_grad_lds_bytes(c, D, K, npass_dir, 1, false) > 150 * 1024)) npass_dir = (npass_dir + 1) / 2;
+    return npass_dir;
+}
+// directions per pass (and the compile-time NPC) of the register-resident kernel (xt_gradr.h)
+static int xt_gradr_per_pass(const extrack_ctx* ctx, int n_dir, int* NPC_out)
+{
+    // 4 directions per pass: with 6 the register allocator spills inside the step loop (3 states: 917 GB of scratch traffic per C3
+    // launch, r03 PMC) and the pass count saved does not pay for it; 3 per pass when that needs no more passes
+    int NPC = ctx->gradr_npc ? ctx->gradr_npc : 4;
+    const int npass = (n_dir + NPC - 1) / NPC, per = (n_dir + npass - 1) / npass;
+    if (per <= 3 && !ctx->gradr_npc) NPC = 3;
+    *NPC_out = NPC;
+    return per;
+}
+
+// Missed detections (extrack_loglik_grad_gaps / extrack_loglik_scores_gaps): the refusals of extrack_loglik_gaps, decided here on the host
+// before anything is enqueued or recorded - nb_substeps >= 2, more than 4 states, buckets with per-track time steps, and models that fit
+// neither the register-resident nor the LDS-resident gap-aware kernel (extrack_grad_gaps.hip).
+static int xt_grad_gaps_check(extrack_ctx* ctx, const extrack_model* m, int n_dir)
+{
+    if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: built for nb_substeps == 1");
+    if (m->n_states < 2 || m->n_states > 4) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: built for 2, 3 and 4 states");
+    XtConfig c;
+    std::string err = xt_build_config(m->n_states, m->nb_substeps, m->frame_len, c);
+    if (!err.empty()) return xt_fail(ctx, EXTRACK_E_INVALID, err);
+    for (const XtBucket& b : ctx->buckets) {
+        if (b.d_dt) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: not built for buckets with per-track time steps");
+        const int D = b.D, K = m->locerr_mode == 0 ? m->locerr_dims : b.KS;
+        if (K != 1 && K != D) return xt_fail(ctx, EXTRACK_E_INVALID, m->locerr_mode == 0 ? "locerr_dims must be 1 or the track dimensionality"
+                                                                                         : "per-peak localisation error mode but the bucket has no sigma");
+        if (ctx->grad_reg2 && c.NG <= 256) {
+            int NPC;
+            const int per = xt_gradr_per_pass(ctx, n_dir, &NPC);
+            if (xt_gradr_gap_kernel_ptr(c.G, D, K, NPC) &&
+                xt_gradr_lds_bytes(c.S, c.G, c.E, c.EP, c.NG, c.P, D, K, per, std::max(1, 256 / c.NG)) <= 160 * 1024)
+                continue;
+        }
+        const int npass_dir = xt_grad_lds_npass_dir(c, D, K, n_dir);
+        bool fits = c.NG <= 1024 && xt_grad_lds_bytes(c, D, K, std::min(npass_dir, n_dir), 1, false) <= 160 * 1024;
+        for (int p0 = 0; fits && p0 < n_dir; p0 += npass_dir) {
+            const XtGradLdsGeom gm = xt_grad_lds_geometry(c, D, K, std::min(npass_dir, n_dir - p0));
+            fits = gm.threads <= 1024 && gm.lds <= 160 * 1024 && xt_grad_gap_kernel_ptr(c.G, D, K, gm.threads > 256) != nullptr;
+        }
+        if (!fits)
+            return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: the model fits neither gap-aware gradient kernel (more than 1024 groups of sequences or more than 160 KiB of LDS per track)");
+    }
+    return EXTRACK_OK;
+}
+
 static int xt_grad_reserve(extrack_ctx* ctx, double** buf, size_t* cap, size_t n)
 {
     if (n <= *cap) return EXTRACK_OK;
@@ -142,12 +237,15 @@ static int xt_grad_reserve(extrack_ctx* ctx, double** buf, size_t* cap, size_t n
 // d_scores (device, [sum N][n_dir], or nullptr): a scores evaluation - the forward-mode kernels also store every track's dLL_n/dtheta, rows
 // in bucket-id order, columns in launch order (cols->idx[c] = the caller's direction of column c); the reverse-mode kernels are bypassed
 // (their adjoints are accumulated across tracks) and d_opg (device, [n_dir][n_dir], or nullptr) receives sum_n s_n s_n^T.
+// gaps: tracks with missed detections (all-NaN rows) - the gap-aware instantiations of the two forward-mode bodies only (extrack_grad_gaps.hip:
+// the register-resident 2-state and the reverse-mode kernels have none), the register-resident one first, then the LDS-resident one.
 static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out,
-                           double* d_scores = nullptr, XtOpgCols* cols = nullptr, double* d_opg = nullptr)
+                           double* d_scores = nullptr, XtOpgCols* cols = nullptr, double* d_opg = nullptr, bool gaps = false)
 {
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (ctx->buckets.empty()) return xt_fail(ctx, EXTRACK_E_INVALID, "no bucket uploaded");
+    if (gaps && (rc = xt_grad_gaps_check(ctx, m, n_dir))) return rc;
     for (int i = 0; i < n_dir; ++i)
         if (!tangents[i].ds2 || !tangents[i].Fs || !tangents[i].TrMat || !tangents[i].p_stay)
             return xt_fail(ctx, EXTRACK_E_INVALID, "null tangent field");
@@ -231,9 +329,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             if (!b0.d_sigma) return xt_fail(ctx, EXTRACK_E_INVALID, "per-peak localisation error mode but the bucket has no sigma");
             K = b0.KS;
         }
-        // directions per pass: as many as keep one track's state within the LDS of a CU (all of them for the usual models)
-        int npass_dir = std::max(n_dir, 1);
-        while (npass_dir > 1 && (npass_dir > 16 || xt_grad_lds_bytes(c, D, K, npass_dir, 1, false) > 150 * 1024)) npass_dir = (npass_dir + 1) / 2;
+        const int npass_dir = xt_grad_lds_npass_dir(c, D, K, n_dir);
         // bucket descriptors of this group (shared by its passes)
         std::vector<XtBucketDesc> descs;
         for (XtBucket* b : g) {
@@ -258,7 +354,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
         XT_HIP(ctx, hipMemcpyAsync(ctx->d_desc + doff, ctx->h_desc + doff, descs.size() * sizeof(XtBucketDesc), hipMemcpyHostToDevice, ctx->stream));
         XT_HIP(ctx, hipEventRecord(ctx->ev_blob[(ctx->blob_turn - 1u) & 1u], ctx->stream));
         // ---- two-state models: register-resident kernels (xt_reg2.h), <= 8 directions per pass, tangents in VGPRs
-        const bool r2 = ctx->grad_reg2 == 1 && xt_use_reg2(c.S, c.NS, c.F) && m->locerr_mode == 0 && n_dir > 0 && xt_r2_kernel(c.F, D, K, 1) != nullptr;
+        const bool r2 = !gaps && ctx->grad_reg2 == 1 && xt_use_reg2(c.S, c.NS, c.F) && m->locerr_mode == 0 && n_dir > 0 && xt_r2_kernel(c.F, D, K, 1) != nullptr;
         // ---- reverse mode (xt_rev.h): one forward + one backward sweep whatever the number of directions; the adjoint of the model blob
         // is contracted with the tangent blocks by a small kernel.  3 / 4 members per group by default (r03: C3, 13 directions)
         {
@@ -274,7 +370,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             for (auto& d : descs) Lmax0 = std::max(Lmax0, (int)d.L);
             const size_t slot_doubles = (size_t)tpb * std::max(Lmax0 - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
             const size_t max_blocks = (ctx->rev_log_mb << 20) / (slot_doubles * sizeof(double));
-            const bool use_rev = !d_scores && kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
+            const bool use_rev = !gaps && !d_scores && kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
                                  (ctx->grad_rev == 2 || (ctx->grad_rev == 1 && ctx->grad_reg2 == 1 && !r2));
             if (use_rev) {
                 if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -427,14 +523,12 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
         // Measured against the LDS-resident kernel below (r03): C3 (3 states, 13 directions) frame_len 6 601 ms vs 1 960 ms, frame_len 4 63 vs 79 ms;
         // C2-type data through the general kernels (2 states with per-peak errors; in the launcher's order reg2 -> rev -> gradr -> lds the reverse-mode
         // kernels above now take those models first) frame_len 6 43.8 vs 52.9 ms, frame_len 4 16.1 vs 16.4 ms.
-        if (ctx->grad_reg2 && n_dir > 0 && c.G >= 2 && c.G <= 4 && c.NG <= 256 && xt_gradr_kernel_ptr(c.G, D, K, 4) != nullptr) {
+        if (ctx->grad_reg2 && n_dir > 0 && c.G >= 2 && c.G <= 4 && c.NG <= 256 &&
+            (gaps ? xt_gradr_gap_kernel_ptr(c.G, D, K, 4) : xt_gradr_kernel_ptr(c.G, D, K, 4)) != nullptr) {
             const int tpb = std::max(1, 256 / c.NG), threads = (tpb * c.NG + 63) / 64 * 64;
-            // 4 directions per pass: with 6 the register allocator spills inside the step loop (3 states: 917 GB of scratch traffic per C3
-            // launch, r03 PMC) and the pass count saved does not pay for it; 3 per pass when that needs no more passes
-            int NPC = ctx->gradr_npc ? ctx->gradr_npc : 4;
-            const int npass = (n_dir + NPC - 1) / NPC, per = (n_dir + npass - 1) / npass;
-            if (per <= 3 && !ctx->gradr_npc) NPC = 3;
-            const void* kp = xt_gradr_kernel_ptr(c.G, D, K, NPC);
+            int NPC;
+            const int per = xt_gradr_per_pass(ctx, n_dir, &NPC);
+            const void* kp = gaps ? xt_gradr_gap_kernel_ptr(c.G, D, K, NPC) : xt_gradr_kernel_ptr(c.G, D, K, NPC);
             const size_t lds = xt_gradr_lds_bytes(c.S, c.G, c.E, c.EP, c.NG, c.P, D, K, per, tpb);
             if (kp && lds <= 160 * 1024) {
                 if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -501,25 +595,12 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             l.ctx = ctx;
             memset(&l.a, 0, sizeof(l.a));
             xt_fill_args_from_config(c, l.a);
-            const bool tan_lds = (size_t)NP * TB * 8 <= 16 * 1024;
-            const size_t per_track = xt_grad_lds_bytes(c, D, K, NP, 1, tan_lds) - xt_grad_lds_bytes(c, D, K, NP, 0, tan_lds);
-            const size_t fixed = xt_grad_lds_bytes(c, D, K, NP, 0, tan_lds);
-            const size_t budget = 64 * 1024;
-            // PJ lanes per group: about two directions per lane, as long as a track's threads fit a workgroup
-            int PJ = 1;
-            while (PJ < 8 && PJ * 2 <= NP && NP > 2 * PJ - 1 && c.NG * PJ * 2 <= 1024) PJ *= 2;
-            if (const char* ev = getenv("EXTRACK_GRAD_PJ")) {
-                const int v = atoi(ev);
-                if ((v == 1 || v == 2 || v == 4 || v == 8) && c.NG * v <= 1024) PJ = v;
-            }
-            const int NT = c.NG * PJ;
-            const int by_threads = NT >= 256 ? 1 : 256 / NT;
-            const int by_lds = budget > fixed + per_track ? (int)((budget - fixed) / per_track) : 1;
-            int tpb = std::max(1, std::min(by_threads, by_lds));
-            const int threads = (tpb * NT + 63) / 64 * 64;
+            const XtGradLdsGeom gm = xt_grad_lds_geometry(c, D, K, NP);
+            const bool tan_lds = gm.tan_lds;
+            const int PJ = gm.PJ, tpb = gm.tpb, threads = gm.threads;
             if (threads > 1024) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "n_states^(frame_len-nb_substeps) > 1024 groups per track is not built");
             l.threads = threads;
-            l.lds = xt_grad_lds_bytes(c, D, K, NP, tpb, tan_lds);
+            l.lds = gm.lds;
             if (l.lds > 160 * 1024) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "sequence state does not fit the 160 KiB LDS of a CU");
             // grid: blocks per bucket in proportion to its work, CUs oversubscribed (as the likelihood launcher does)
             const int occ = std::max(1, std::min((int)((160 * 1024) / l.lds), 2048 / threads));
@@ -546,7 +627,7 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
             l.ga.PJ = PJ;
             l.ga.score_ld = n_dir;
             l.ga.score_col0 = p0;
-            if (!xt_grad_dispatch(c.G, D, K, l)) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
+            if (!(gaps ? l.run_gaps(c.G, D, K) : xt_grad_dispatch(c.G, D, K, l))) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
             if (l.herr != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("gradient kernel launch: ") + hipGetErrorString(l.herr));
             if (NP > 16) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "more than 16 directions per pass");
             hipLaunchKernelGGL(xt_grad_reduce, dim3(NP + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, l.grid, NP + 1,
@@ -582,20 +663,47 @@ extern "C" int extrack_loglik_grad_async(extrack_ctx* ctx, const extrack_model* 
     return xt_grad_enqueue(ctx, m, n_dir, tangents, d_out);
 }
 
-extern "C" int extrack_loglik_grad(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
-                                   double* total_ll, double* grad)
+extern "C" int extrack_loglik_grad_gaps_async(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                              double* d_out)
+{
+    if (!ctx || !d_out || n_dir < 0 || (n_dir > 0 && !tangents)) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
+    if (n_dir == 0) {  // no direction: the gap-aware likelihood kernels (which have no enqueue-only entry point: the sum is copied to d_out)
+        double ll = 0.0;
+        const int rc = extrack_loglik_gaps(ctx, m, &ll, nullptr);
+        if (rc) return rc;
+        XT_HIP(ctx, hipMemcpyAsync(d_out, &ll, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return EXTRACK_OK;
+    }
+    return xt_grad_enqueue(ctx, m, n_dir, tangents, d_out, nullptr, nullptr, nullptr, true);
+}
+
+static int xt_loglik_grad_sync(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* total_ll,
+                               double* grad, bool gaps)
 {
     if (!ctx || !total_ll || n_dir < 0 || (n_dir > 0 && (!tangents || !grad))) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
-    if (n_dir == 0) return extrack_loglik(ctx, m, total_ll, nullptr);  // no direction: the plain likelihood kernels
+    if (n_dir == 0) return gaps ? extrack_loglik_gaps(ctx, m, total_ll, nullptr) : extrack_loglik(ctx, m, total_ll, nullptr);  // no direction: the likelihood kernels
     int rc = xt_grad_reserve(ctx, &ctx->d_gout, &ctx->gout_cap, (size_t)n_dir + 1);
     if (rc) return rc;
-    if ((rc = xt_grad_enqueue(ctx, m, n_dir, tangents, ctx->d_gout))) return rc;
+    if ((rc = xt_grad_enqueue(ctx, m, n_dir, tangents, ctx->d_gout, nullptr, nullptr, nullptr, gaps))) return rc;
     std::vector<double> host((size_t)n_dir + 1);
     XT_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gout, host.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *total_ll = host[0];
     for (int i = 0; i < n_dir; ++i) grad[i] = host[1 + i];
     return EXTRACK_OK;
+}
+
+extern "C" int extrack_loglik_grad(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                   double* total_ll, double* grad)
+{
+    return xt_loglik_grad_sync(ctx, m, n_dir, tangents, total_ll, grad, false);
+}
+
+extern "C" int extrack_loglik_grad_gaps(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                        double* total_ll, double* grad)
+{
+    return xt_loglik_grad_sync(ctx, m, n_dir, tangents, total_ll, grad, true);
 }
 
 // Validation + the device score matrix [sum N][n_dir] of a scores evaluation (kept with the context)
@@ -609,18 +717,30 @@ static int xt_scores_prepare(extrack_ctx* ctx, int32_t n_dir, const extrack_mode
     return xt_grad_reserve(ctx, &ctx->d_scores, &ctx->scores_cap, (size_t)n_total * n_dir);
 }
 
-extern "C" int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
-                                           double* d_out)
+static int xt_loglik_scores_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out,
+                                    bool gaps)
 {
     if (!ctx || !d_out) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
     int rc = xt_scores_prepare(ctx, n_dir, tangents);
     if (rc) return rc;
     XtOpgCols cols;
-    return xt_grad_enqueue(ctx, m, n_dir, tangents, d_out, ctx->d_scores, &cols, d_out + 1 + n_dir);
+    return xt_grad_enqueue(ctx, m, n_dir, tangents, d_out, ctx->d_scores, &cols, d_out + 1 + n_dir, gaps);
 }
 
-extern "C" int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
-                                     double* total_ll, double* grad, double* opg, double* scores)
+extern "C" int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                           double* d_out)
+{
+    return xt_loglik_scores_enqueue(ctx, m, n_dir, tangents, d_out, false);
+}
+
+extern "C" int extrack_loglik_scores_gaps_async(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                                double* d_out)
+{
+    return xt_loglik_scores_enqueue(ctx, m, n_dir, tangents, d_out, true);
+}
+
+static int xt_loglik_scores_sync(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* total_ll,
+                                 double* grad, double* opg, double* scores, bool gaps)
 {
     if (!ctx || !total_ll) return xt_fail(ctx, EXTRACK_E_INVALID, "null argument");
     int rc = xt_scores_prepare(ctx, n_dir, tangents);
@@ -628,7 +748,7 @@ extern "C" int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* m, i
     const size_t nd = (size_t)n_dir;
     if ((rc = xt_grad_reserve(ctx, &ctx->d_gout, &ctx->gout_cap, 1 + nd + nd * nd))) return rc;
     XtOpgCols cols;
-    if ((rc = xt_grad_enqueue(ctx, m, n_dir, tangents, ctx->d_gout, ctx->d_scores, &cols, opg ? ctx->d_gout + 1 + nd : nullptr))) return rc;
+    if ((rc = xt_grad_enqueue(ctx, m, n_dir, tangents, ctx->d_gout, ctx->d_scores, &cols, opg ? ctx->d_gout + 1 + nd : nullptr, gaps))) return rc;
     std::vector<double> host(1 + nd + nd * nd);
     XT_HIP(ctx, hipMemcpyAsync(host.data(), ctx->d_gout, (opg ? host.size() : 1 + nd) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (scores) {
@@ -651,6 +771,18 @@ extern "C" int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* m, i
     if (opg)
         for (size_t i = 0; i < nd * nd; ++i) opg[i] = host[1 + nd + i];
     return EXTRACK_OK;
+}
+
+extern "C" int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                     double* total_ll, double* grad, double* opg, double* scores)
+{
+    return xt_loglik_scores_sync(ctx, m, n_dir, tangents, total_ll, grad, opg, scores, false);
+}
+
+extern "C" int extrack_loglik_scores_gaps(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents,
+                                          double* total_ll, double* grad, double* opg, double* scores)
+{
+    return xt_loglik_scores_sync(ctx, m, n_dir, tangents, total_ll, grad, opg, scores, true);
 }
 
 extern "C" int extrack_last_grad_ms(extrack_ctx* ctx, float* ms)

@@ -53,7 +53,10 @@ XT_HD int xt_grad_region_doubles(int EP, int D, int K, int NP) { return 2 * xt_r
 // per track slot: block accumulators bacc[NP + 1], column sums csum[NP + 1], per-thread partials gth[NP + 1][NG]
 XT_HD int xt_grad_acc_doubles(int NP, int NG) { return 2 * (NP + 2) + (NP + 1) * NG; }
 
-template <int G_, int D, int K, class Ctx>
+// GAPS (extrack_loglik_grad_gaps): rows whose coordinates are all NaN are missed detections, staged and counted as in
+// xt_track_body<..., GAPS = true>; at such a step the merge is followed by the transition alone:
+//     z' = W T[q],  m' = m_bar,  u' = d2_q + u_bar;     rz' = R + dlogT[q],  dm' = d m_bar,  du' = d d2_q + d u_bar
+template <int G_, int D, int K, bool GAPS = false, class Ctx>
 XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 {
     int lb, nb;
@@ -86,6 +89,7 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     double* reg = smem + reg0 + (tvalid ? slot : 0) * rdoubles;
     const int pdoubles = xt_region_doubles(EP, D, K);
     int* red_e = (int*)(reg + EP * (1 + D + K)) + ((EP + 1) & ~1);  // [0] final-reduce exponent, [1] NaN-input flag (in region 0)
+    double* ngap = (double*)(red_e + 2);  // GAPS: missed detections of the track (region 0's last double, spare without the flag)
     double* tan = reg + 2 * pdoubles;  // [NP][(1 + D + K)][EP]: rz, dm[D], du[K]
     const int tstride = (1 + D + K) * EP;
     const int adoubles = xt_grad_acc_doubles(NP, NG);
@@ -106,6 +110,7 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (tvalid)
         for (int i = rr_; i < NP + 1; i += NT) bacc[i] = 0.0;
     if (tvalid && rr_ == 0) red_e[1] = 0;
+    if (GAPS && tvalid && rr_ == 0) *ngap = 0.0;
     cx.sync();
 
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
@@ -116,6 +121,33 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         const double* sg = b.sigma ? b.sigma + (act ? trk : 0) * (int64_t)L * a.KS : nullptr;
 
         auto stage = [&](int p0) {
+            if (GAPS) {
+                // row by row: all coordinates NaN = a gap (counted; its error is copied but never looked at), some = a NaN input
+                if (act) {
+                    double ng = 0.0;
+                    for (int r = rr_; r < XT_STAGE; r += NT)
+                        if (p0 + r < L) {
+                            int nn = 0;
+                            for (int d = 0; d < D; ++d) {
+                                const double v = c[(p0 + r) * D + d];
+                                spos[r * D + d] = v;
+                                nn += v != v ? 1 : 0;
+                            }
+                            const bool gap = nn == D;
+                            if ((nn != 0 && !gap) || (gap && (p0 + r == 0 || p0 + r == L - 1))) red_e[1] = 1;
+                            ng += gap ? 1.0 : 0.0;
+                            if (sg)
+                                for (int k = 0; k < a.KS; ++k) {
+                                    const double v = sg[(p0 + r) * a.KS + k];
+                                    ssig[r * a.KS + k] = v;
+                                    if (!gap && v != v) red_e[1] = 1;
+                                }
+                        }
+                    if (ng != 0.0) cx.atomic_add_f64(ngap, ng);
+                }
+                cx.sync();
+                return;
+            }
             if (act) {
                 for (int i = rr_; i < XT_STAGE * D; i += NT)
                     if (p0 + i / D < L) {
@@ -208,7 +240,8 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 const int32_t* off = a.off_tab + ph * G;
                 double ct[D], l2t[K], sct[K], srt[K];
                 for (int d = 0; d < D; ++d) ct[d] = spos[(t & (XT_STAGE - 1)) * D + d];
-                load_l2(t, l2t, sct, srt);
+                const bool gap = GAPS && ct[0] != ct[0];  // staged rows are all-NaN or poison the track: the first coordinate decides
+                if (!gap) load_l2(t, l2t, sct, srt);      // (the error of a gap row may be NaN: never read)
                 const bool stay = t >= stay_from;
                 const double* TTl = stay ? T1 : T0;
                 const int tv = (stay ? 1 : 0) * SG + toff;
@@ -259,7 +292,7 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         tt[k] = s2 * r[k];
                     }
                 };
-                if (G_)
+                if (G_ && !gap)
                     for (int q = 0; q < GM; ++q) light(q, rq[q], tq[q]);
 
                 // tangents of this lane's directions (reads the OLD primal members, writes the new tangents in place)
@@ -286,6 +319,16 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                             const double uv = G_ ? uj[G_ ? q : 0][k] : uu[k * EP + idx];
                             dub[k] = xt_fma(aq, xt_fma(uv - ub[k], rzq, tp[(1 + D + k) * EP + idx]), dub[k]);
                         }
+                    }
+                    if (GAPS && gap) {  // a branch, not selects: no l2, dl2, reciprocal or quadratic form at a row that was not observed
+                        for (int q = 0; q < G; ++q) {
+                            const int idx = xt_skew(base + off[q], a.skew);
+                            const double dd2 = dtb[4 * SG + toff + q];
+                            tp[idx] = W > 0.0 ? R + dtb[tv + q] : 0.0;
+                            for (int d = 0; d < D; ++d) tp[(1 + d) * EP + idx] = dmb[d];
+                            for (int k = 0; k < K; ++k) tp[(1 + D + k) * EP + idx] = dd2 + dub[k];
+                        }
+                        continue;
                     }
                     double dl2[K];
                     dl2_of(dtb, sct, srt, dl2);
@@ -329,7 +372,16 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 // primal update (as xt_track_body), by lane j == 0 of the group
                 const double Wm = xt_frexp_mant(W);
                 const int We = W > 0.0 ? emax + xt_frexp_exp(W) : XT_EMIN;
-                for (int q = 0; q < (j == 0 ? G : 0); ++q) {
+                if (GAPS && gap) {  // transition-only step
+                    for (int q = 0; q < (j == 0 ? G : 0); ++q) {
+                        const int idx = xt_skew(base + off[q], a.skew);
+                        zmN[idx] = Wm * TTl[q];
+                        zeN[idx] = We;
+                        for (int d = 0; d < D; ++d) mmN[d * EP + idx] = mb[d];
+                        for (int k = 0; k < K; ++k) uuN[k * EP + idx] = TD2[q] + ub[k];
+                    }
+                }
+                for (int q = 0; q < (j == 0 && !gap ? G : 0); ++q) {
                     const int idx = xt_skew(base + off[q], a.skew);
                     double rl[K], tl[K];
                     const double* r = rl;
@@ -491,7 +543,11 @@ XT_HD void xt_grad_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int fe = red_e[0];
             for (int col = rr_; col < NP + 1; col += NT) {
                 if (col == 0) {
-                    const double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                    double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                    if (GAPS) {  // b.ll_const counts every row of the bucket: give back the missed ones' share (no parameter in it: the scores get nothing)
+                        ll += *ngap * (0.5 * D * XT_LOG2PI);
+                        *ngap = 0.0;  // for the next batch (only this thread reads it, and no row is staged before the barrier below)
+                    }
                     if (b.ll_out) b.ll_out[trk] = ll;
                     bacc[0] += ll;
                 } else {

@@ -33,7 +33,9 @@ XT_HD size_t xt_gradr_lds_bytes(int S, int G, int E, int EP, int NG, int P, int 
     return ((size_t)xt_gradr_fixed_doubles(S, G, NP, P, NG) + (size_t)tpb * ((size_t)xt_gradr_track_doubles(EP, D, K, NP) + xt_stage_doubles(D))) * sizeof(double);
 }
 
-template <int G_, int D, int K, int NPC, class Ctx>
+// GAPS (extrack_loglik_grad_gaps): a row whose coordinates are all NaN is a missed detection, staged and counted as in
+// xt_track_body<..., GAPS = true>; its step carries the merge's tangents through the transition alone (no Gaussian factor, no l2 / dl2).
+template <int G_, int D, int K, int NPC, bool GAPS = false, class Ctx>
 XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 {
     int lb, nb;
@@ -69,6 +71,7 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     double* bacc = tr0 + 2 * xdoubles;   // [NP + 1] (+ pad)
     double* csum = bacc + NP + 2;        // [NP + 1] (+ pad)
     int* red_e = (int*)(csum + NP + 2);  // [0] final-reduce exponent, [1] NaN-input flag
+    double* ngap = (double*)(red_e + 2);  // GAPS: missed detections of the track (the slot's last double, spare without the flag)
     double* gth = X[0];                  // per-thread partials [NP + 1][NG] of the final reduction (the exchange buffers are idle then)
     double* spos = smem + reg0 + a.TPB * tdoubles + (tvalid ? slot : 0) * xt_stage_doubles(D);
     double* ssig = spos + XT_STAGE * D;
@@ -85,6 +88,7 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (tvalid)
         for (int i = g; i < NP + 1; i += NG) bacc[i] = 0.0;
     if (tvalid && g == 0) red_e[1] = 0;
+    if (GAPS && tvalid && g == 0) *ngap = 0.0;
     cx.sync();
 
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
@@ -95,6 +99,33 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         const double* sg = b.sigma ? b.sigma + (act ? trk : 0) * (int64_t)L * a.KS : nullptr;
 
         auto stage = [&](int p0) XT_INL {
+            if (GAPS) {
+                // row by row: all coordinates NaN = a gap (counted; its error is copied but never looked at), some = a NaN input
+                if (act) {
+                    double ng = 0.0;
+                    for (int r = g; r < XT_STAGE; r += NG)
+                        if (p0 + r < L) {
+                            int nn = 0;
+                            for (int d = 0; d < D; ++d) {
+                                const double v = c[(p0 + r) * D + d];
+                                spos[r * D + d] = v;
+                                nn += v != v ? 1 : 0;
+                            }
+                            const bool gap = nn == D;
+                            if ((nn != 0 && !gap) || (gap && (p0 + r == 0 || p0 + r == L - 1))) red_e[1] = 1;
+                            ng += gap ? 1.0 : 0.0;
+                            if (sg)
+                                for (int k = 0; k < a.KS; ++k) {
+                                    const double v = sg[(p0 + r) * a.KS + k];
+                                    ssig[r * a.KS + k] = v;
+                                    if (!gap && v != v) red_e[1] = 1;
+                                }
+                        }
+                    if (ng != 0.0) cx.atomic_add_f64(ngap, ng);
+                }
+                cx.sync();
+                return;
+            }
             if (act) {
                 for (int i = g; i < XT_STAGE * D; i += NG)
                     if (p0 + i / D < L) {
@@ -196,7 +227,7 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             double ct[D], l2t[K], sct[K], srt[K];
             // shared primal factors of the tangent updates
             double aj[G], mjc[G][D], ujc[G][K], dn[D], rq[G][K], tq[G][K], Aq[G][K];
-            bool liveW = false;
+            bool liveW = false, gap = false;
             const bool stay = t >= stay_from;
             const int tv = (stay ? 1 : 0) * SG + toff;
             {
@@ -208,7 +239,8 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 }
                 XT_UNROLL
                 for (int d = 0; d < D; ++d) ct[d] = spos[(t & (XT_STAGE - 1)) * D + d];
-                load_l2(t, l2t, sct, srt);
+                gap = GAPS && ct[0] != ct[0];  // staged rows are all-NaN or poison the track: the first coordinate decides
+                if (!gap) load_l2(t, l2t, sct, srt);  // (the error of a gap row may be NaN: never read)
                 const double* TTl = stay ? T1 : T0;
 
                 // primal merge
@@ -253,41 +285,53 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 const int We = liveW ? emax + xt_frexp_exp(W) : XT_EMIN;
                 // round 0: the new primal sequences (as xt_track_body) -> exchange buffer 0
                 int* xz = XZ(0);
-                XT_UNROLL
-                for (int q = 0; q < G; ++q) {
-                    const double d2 = TD2[q];
-                    double quad, gf;
-                    if (K == 1) {
-                        const double s2 = d2 + ub[0];
-                        rq[q][0] = xt_rcp(l2t[0] + s2);
-                        tq[q][0] = s2 * rq[q][0];
-                        quad = 0.5 * dsq * rq[q][0];
-                        gf = xt_pow_half<D>(rq[q][0]);
-                        Aq[q][0] = -0.5 * rq[q][0] * xt_fma(-dsq, rq[q][0], (double)D);
-                    } else {
-                        quad = 0.0;
-                        gf = 1.0;
+                if (GAPS && gap) {  // transition-only step: a branch, not selects (lanes of another track may take the other side at the same t)
+                    XT_UNROLL
+                    for (int q = 0; q < G; ++q) {
+                        X[0][widx[q]] = Wm * TTl[q];
+                        xz[widx[q]] = We;
                         XT_UNROLL
-                        for (int d = 0; d < D; ++d) {
-                            const double s2 = d2 + ub[d];
-                            rq[q][d] = xt_rcp(l2t[d] + s2);
-                            tq[q][d] = s2 * rq[q][d];
-                            quad = xt_fma(0.5 * dn[d] * dn[d], rq[q][d], quad);
-                            gf *= rq[q][d];
-                            Aq[q][d] = -0.5 * rq[q][d] * xt_fma(-(dn[d] * dn[d]), rq[q][d], 1.0);
-                        }
-                        gf = sqrt(gf);
+                        for (int d = 0; d < D; ++d) X[0][(1 + d) * EP + widx[q]] = mb[d];
+                        XT_UNROLL
+                        for (int k = 0; k < K; ++k) X[0][(1 + D + k) * EP + widx[q]] = TD2[q] + ub[k];
                     }
-                    double pp;
-                    int jt, n;
-                    xt_exp_tab(-quad, pp, jt, n);
-                    const int en = We + n;
-                    X[0][widx[q]] = (Wm * TTl[q]) * (gf * T64[jt]) * pp;
-                    xz[widx[q]] = en > XT_EMIN ? en : XT_EMIN;
+                } else {
                     XT_UNROLL
-                    for (int d = 0; d < D; ++d) X[0][(1 + d) * EP + widx[q]] = xt_fma(dn[d], tq[q][K == 1 ? 0 : d], mb[d]);
-                    XT_UNROLL
-                    for (int k = 0; k < K; ++k) X[0][(1 + D + k) * EP + widx[q]] = l2t[k] * tq[q][k];
+                    for (int q = 0; q < G; ++q) {
+                        const double d2 = TD2[q];
+                        double quad, gf;
+                        if (K == 1) {
+                            const double s2 = d2 + ub[0];
+                            rq[q][0] = xt_rcp(l2t[0] + s2);
+                            tq[q][0] = s2 * rq[q][0];
+                            quad = 0.5 * dsq * rq[q][0];
+                            gf = xt_pow_half<D>(rq[q][0]);
+                            Aq[q][0] = -0.5 * rq[q][0] * xt_fma(-dsq, rq[q][0], (double)D);
+                        } else {
+                            quad = 0.0;
+                            gf = 1.0;
+                            XT_UNROLL
+                            for (int d = 0; d < D; ++d) {
+                                const double s2 = d2 + ub[d];
+                                rq[q][d] = xt_rcp(l2t[d] + s2);
+                                tq[q][d] = s2 * rq[q][d];
+                                quad = xt_fma(0.5 * dn[d] * dn[d], rq[q][d], quad);
+                                gf *= rq[q][d];
+                                Aq[q][d] = -0.5 * rq[q][d] * xt_fma(-(dn[d] * dn[d]), rq[q][d], 1.0);
+                            }
+                            gf = sqrt(gf);
+                        }
+                        double pp;
+                        int jt, n;
+                        xt_exp_tab(-quad, pp, jt, n);
+                        const int en = We + n;
+                        X[0][widx[q]] = (Wm * TTl[q]) * (gf * T64[jt]) * pp;
+                        xz[widx[q]] = en > XT_EMIN ? en : XT_EMIN;
+                        XT_UNROLL
+                        for (int d = 0; d < D; ++d) X[0][(1 + d) * EP + widx[q]] = xt_fma(dn[d], tq[q][K == 1 ? 0 : d], mb[d]);
+                        XT_UNROLL
+                        for (int k = 0; k < K; ++k) X[0][(1 + D + k) * EP + widx[q]] = l2t[k] * tq[q][k];
+                    }
                 }
             }
             cx.sync();
@@ -326,33 +370,45 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         XT_UNROLL
                         for (int k = 0; k < K; ++k) dub[k] = xt_fma(aj[Q], xt_fma(ujc[Q][k], rzq, tdu[p][Q][k]), dub[k]);
                     }
-                    double dl2[K], hd[K];  // hd: -1/2 d |c - m_bar|^2 (per dim when K == D)
-                    dl2_of(dtb, sct, srt, dl2);
-                    if (K == 1) {
-                        hd[0] = 0.0;
+                    if (GAPS && gap) {  // rz' = R + d log T, dm' = d m_bar, du' = d d2 + d u_bar: no l2, dl2, reciprocal or quadratic form
                         XT_UNROLL
-                        for (int d = 0; d < D; ++d) hd[0] = xt_fma(dn[d], dmb[d], hd[0]);
-                    } else {
-                        XT_UNROLL
-                        for (int d = 0; d < D; ++d) hd[d] = dn[d] * dmb[d];
-                    }
-                    XT_UNROLL
-                    for (int q = 0; q < G; ++q) {
-                        const double dd2 = dtb[4 * SG + toff + q];
-                        double rz = R + dtb[tv + q], dtt[K];
-                        XT_UNROLL
-                        for (int k = 0; k < K; ++k) {
-                            const double ds2 = dd2 + dub[k], dden = dl2[k] + ds2;
-                            dtt[k] = rq[q][k] * xt_fma(-tq[q][k], dden, ds2);
-                            rz = xt_fma(Aq[q][k], dden, rz);
-                            rz = xt_fma(rq[q][k], hd[k], rz);
-                            xb[(1 + D + k) * EP + widx[q]] = xt_fma(l2t[k], dtt[k], dl2[k] * tq[q][k]);
+                        for (int q = 0; q < G; ++q) {
+                            const double dd2 = dtb[4 * SG + toff + q];
+                            xb[widx[q]] = liveW ? R + dtb[tv + q] : 0.0;
+                            XT_UNROLL
+                            for (int d = 0; d < D; ++d) xb[(1 + d) * EP + widx[q]] = dmb[d];
+                            XT_UNROLL
+                            for (int k = 0; k < K; ++k) xb[(1 + D + k) * EP + widx[q]] = dd2 + dub[k];
                         }
-                        xb[widx[q]] = liveW ? rz : 0.0;
+                    } else {
+                        double dl2[K], hd[K];  // hd: -1/2 d |c - m_bar|^2 (per dim when K == D)
+                        dl2_of(dtb, sct, srt, dl2);
+                        if (K == 1) {
+                            hd[0] = 0.0;
+                            XT_UNROLL
+                            for (int d = 0; d < D; ++d) hd[0] = xt_fma(dn[d], dmb[d], hd[0]);
+                        } else {
+                            XT_UNROLL
+                            for (int d = 0; d < D; ++d) hd[d] = dn[d] * dmb[d];
+                        }
                         XT_UNROLL
-                        for (int d = 0; d < D; ++d) {
-                            const int kk = K == 1 ? 0 : d;
-                            xb[(1 + d) * EP + widx[q]] = xt_fma(dn[d], dtt[kk], xt_fma(-tq[q][kk], dmb[d], dmb[d]));
+                        for (int q = 0; q < G; ++q) {
+                            const double dd2 = dtb[4 * SG + toff + q];
+                            double rz = R + dtb[tv + q], dtt[K];
+                            XT_UNROLL
+                            for (int k = 0; k < K; ++k) {
+                                const double ds2 = dd2 + dub[k], dden = dl2[k] + ds2;
+                                dtt[k] = rq[q][k] * xt_fma(-tq[q][k], dden, ds2);
+                                rz = xt_fma(Aq[q][k], dden, rz);
+                                rz = xt_fma(rq[q][k], hd[k], rz);
+                                xb[(1 + D + k) * EP + widx[q]] = xt_fma(l2t[k], dtt[k], dl2[k] * tq[q][k]);
+                            }
+                            xb[widx[q]] = liveW ? rz : 0.0;
+                            XT_UNROLL
+                            for (int d = 0; d < D; ++d) {
+                                const int kk = K == 1 ? 0 : d;
+                                xb[(1 + d) * EP + widx[q]] = xt_fma(dn[d], dtt[kk], xt_fma(-tq[q][kk], dmb[d], dmb[d]));
+                            }
                         }
                     }
                 }
@@ -481,7 +537,11 @@ XT_HD void xt_gradr_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int fe = red_e[0];
             for (int col = g; col < NP + 1; col += NG) {
                 if (col == 0) {
-                    const double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                    double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                    if (GAPS) {  // b.ll_const counts every row of the bucket: give back the missed ones' share (no parameter in it: the scores get nothing)
+                        ll += *ngap * (0.5 * D * XT_LOG2PI);
+                        *ngap = 0.0;  // for the next batch (only this thread reads it, and no row is staged before the barrier below)
+                    }
                     if (b.ll_out) b.ll_out[trk] = ll;
                     bacc[0] += ll;
                 } else {

@@ -433,3 +433,6 @@ int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucke
 int xt_refine_fixed_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, const int8_t* states, double* mu, double* sigma,
                                   double* logdens, bool gaps);
 const void* xt_gradr_kernel_ptr(int G, int D, int K, int NPC);  // extrack_gradr.hip: register-resident gradient kernels (xt_gradr.h), NPC = 3 | 4
+// extrack_grad_gaps.hip: gap-aware instantiations of xt_gradr_body (NPC = 3 | 4) and of xt_grad_body (wide: more than 256 threads), nullptr = not built
+const void* xt_gradr_gap_kernel_ptr(int G, int D, int K, int NPC);
+const void* xt_grad_gap_kernel_ptr(int G, int D, int K, bool wide);

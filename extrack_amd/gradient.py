@@ -179,9 +179,16 @@ def objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, fr
     a NaN objective (a NaN position or localisation error poisons its track's LL in the kernels), as ``cum_Proba_Cs`` maps NaN to +inf.
     ``comm``: extrack_amd.distributed.Comm - the (1 + nvar) vector is all-reduced over the ranks.
     ``threshold_fusion``: None = the fixed-window objective; (threshold, max_nb_states, chunk) = the threshold-fusion objective of
-    extrack/tracking.py:427-743 and its gradient at the frozen plan of this evaluation (extrack_loglik_th_grad)."""
-    from .tracking import _objective_model
+    extrack/tracking.py:427-743 and its gradient at the frozen plan of this evaluation (extrack_loglik_th_grad).
+    A ``TrackSet`` with ``.gaps`` (missed detections as all-NaN rows) goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps);
+    they are built for the fixed-window objective on one GPU: ``threshold_fusion`` or ``comm`` raise NotImplementedError."""
+    from .tracking import _GAPS_NO_COMM, _GAPS_NO_THRESHOLD, _objective_model
     names = free_names(params) if names is None else list(names)
+    gaps = bool(getattr(ts, "gaps", False))
+    if gaps and threshold_fusion is not None:
+        raise NotImplementedError(_GAPS_NO_THRESHOLD)
+    if gaps and comm is not None:
+        raise NotImplementedError(_GAPS_NO_COMM)
     if ts.has_dt and threshold_fusion is not None:
         raise NotImplementedError("the frozen-plan gradient does not serve per-track time steps: use gradient='fd'")
     model = _objective_model(params, ts, dt, cell_dims, None, nb_states, nb_substeps, frame_len, Matrix_type)
@@ -207,7 +214,7 @@ def objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, fr
     elif comm is not None:
         v = comm.allreduce_loglik_grad(ts, model, tang, len(names))
     elif ts.n_tracks:
-        ll, g = ts.ctx.loglik_grad(model, tang)
+        ll, g = ts.ctx.loglik_grad(model, tang, gaps=True) if gaps else ts.ctx.loglik_grad(model, tang)
         v = np.concatenate([[ll], g])
     else:
         v = np.zeros(1 + len(names))

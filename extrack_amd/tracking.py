@@ -452,15 +452,14 @@ def cum_Proba_Cs_grad(params, names, all_tracks, dt, cell_dims, input_LocErr, nb
     (extrack/tracking.py:1371).  ``fusion="window"``: extrack_loglik_grad; ``fusion="threshold"`` (what extrack.tracking.param_fitting
     minimises in v1.6.3): extrack_loglik_th_grad - the value is that of ``cum_Proba_Cs(..., fusion="threshold")`` and the gradient its
     derivative with the merge groups of THIS evaluation held fixed (the plan is re-decided at every call, exactly as the objective does).
-    Same argument list as ``cum_Proba_Cs`` after ``names``; same prints; (+inf, zeros) for invalid parameters or NaN."""
+    Same argument list as ``cum_Proba_Cs`` after ``names``; same prints; (+inf, zeros) for invalid parameters or NaN.
+    A ``TrackSet`` with ``gaps=True`` goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps; fusion="window", no ``comm``)."""
     from . import gradient
     th = _check_fusion(fusion)
     if th and comm is not None and not isinstance(all_tracks, TrackSet):
         raise ValueError("fusion='threshold' with comm needs chunk-aligned shards: pass the TrackSet of comm.shard_trackset(..., chunk=...)")
     ts, owned = _as_trackset(all_tracks, input_LocErr, device, comm)
     try:
-        if ts.gaps:
-            raise NotImplementedError("gaps=True: the gradient kernels have no gap-aware variant")
         out, g = gradient.objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, frame_len, Matrix_type, comm, names,
                                                  threshold_fusion=(threshold, max_nb_states, max_number_of_tracks_per_matrix) if th else None)
     finally:
@@ -640,20 +639,27 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     ``fit.covar``, ``fit.params[name].stderr`` / ``.correl``, ``fit.errorbars``, ``fit.uncertainty_method``, ``fit.uncertainty_message``;
     fixed-window kernel with a scalar ``dt`` only), ``gaps`` (True: rows of ``all_tracks`` whose coordinates are all NaN are missed
     detections and the bucket keys are frame spans, as ``extrack_amd.gaps.insert_gaps`` makes them; the positions are integrated out
-    exactly, DESIGN.md section 18.  Such fits difference the objective - ``gradient=None`` resolves to "fd" - and are built for
-    fusion="window" on one GPU without ``uncertainties``)."""
+    exactly, DESIGN.md section 18.  Such fits difference the objective by default - ``gradient=None`` resolves to "fd" - and take the exact
+    gradient of the gap-aware forward-mode kernels with ``gradient="forward"`` (a value that exists with ``gaps`` only).
+    They are built for fusion="window" on one GPU; ``gradient="analytic"`` and ``uncertainties`` stay refused with ``gaps`` - standard errors
+    come from ``uncertainty.parameter_uncertainties(..., gaps=True)`` and ``uncertainty.attach``)."""
     from . import uncertainty
     fusion = "threshold" if _check_fusion(fusion) else "window"
     unc_method = uncertainty.resolve_method(uncertainties)
+    forward = bool(gaps) and gradient == "forward"  # the gap-aware forward-mode gradient: opt-in, exists with gaps only
+    if gradient not in (None, "analytic", "fd") and not forward:
+        raise ValueError("gradient must be None, 'analytic' or 'fd' (or, with gaps=True, 'forward': the gap-aware forward-mode kernels)")
     if gaps:
         if fusion == "threshold":
             raise NotImplementedError(_GAPS_NO_THRESHOLD)
         if comm is not None:
             raise NotImplementedError(_GAPS_NO_COMM)
         if gradient == "analytic":
-            raise NotImplementedError("gaps=True: the gradient kernels have no gap-aware variant; use gradient=None or 'fd'")
+            raise NotImplementedError("gaps=True: gradient='analytic' (the register-resident and reverse-mode kernels it selects) has no "
+                                      "gap-aware variant; use gradient='forward' (the gap-aware forward-mode kernels), None or 'fd'")
         if unc_method is not None:
-            raise NotImplementedError("gaps=True: uncertainties need per-track scores, which have no gap-aware kernel")
+            raise NotImplementedError("gaps=True: param_fitting does not attach uncertainties to a gapped fit; call "
+                                      "uncertainty.parameter_uncertainties(..., gaps=True) on the fitted parameters and uncertainty.attach")
     if unc_method is not None and (fusion == "threshold" or isinstance(dt, (dict, list))):
         raise NotImplementedError("uncertainties need per-track scores, which the fixed-window kernels with a scalar dt provide: "
                                   "not built for fusion='threshold' or per-track time steps")
@@ -679,18 +685,26 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
         ts = TrackSet(tracks, sigmas, device=device, dts=dts, gaps=gaps)
     from . import lmfit_compat
     can_grad = str(method).lower() in lmfit_compat._GRADIENT_METHODS and not (fusion == "threshold" and dts is not None)
-    if gradient not in (None, "analytic", "fd"):
-        raise ValueError("gradient must be None, 'analytic' or 'fd'")
     if gradient == "analytic" and not can_grad:
         raise ValueError("gradient='analytic' needs a gradient-based method (and, with fusion='threshold', a scalar dt)")
+    if forward and not can_grad:
+        ts.close()
+        raise ValueError("gradient='forward' needs a gradient-based method")
     fargs = (ts, dt, cell_dims, sigmas, nb_states, nb_substeps, frame_len, verbose, workers, Matrix_type, threshold, max_nb_states, 2000,
              comm, fusion)
     ginfo = {"gradient_path": "fd", "gradient_why": "requested (gradient='fd')" if gradient == "fd" else "method %r takes no gradient" % method}
     if gaps and gradient is None:
-        ginfo["gradient_why"] = "gaps=True: the gradient kernels have no gap-aware variant, the objective is differenced"
+        ginfo["gradient_why"] = ("gaps=True: the objective is differenced by default; gradient='forward' fits with the exact gradient of the "
+                                 "gap-aware forward-mode kernels")
     try:
-        use_grad = can_grad and gradient != "fd" and not gaps
-        if use_grad:
+        use_grad = forward or (can_grad and gradient != "fd" and not gaps)
+        if forward:
+            from . import gradient as _gradient
+            why = _gradient.analytic_support(params, _gradient.free_names(params))
+            if why is not None:
+                raise ValueError("gradient='forward': a parameter expression is not differentiable (%s)" % why)
+            ginfo["gradient_path"], ginfo["gradient_why"] = "analytic", "requested (gradient='forward'): the gap-aware forward-mode kernels"
+        elif use_grad:
             use_grad = _pick_gradient(params, fargs, explicit=(gradient == "analytic"), comm=comm, info=ginfo)
         if use_grad and fusion == "threshold":
             fit = _fit_threshold_frozen_plan(params, fargs, method, ts)

@@ -178,15 +178,15 @@ def _own(params):
     return params if isinstance(params, _OwnParameters) else _to_own_parameters(params)
 
 
-def _open(all_tracks, dt, input_LocErr, device):
-    """(TrackSet, owned, bucket keys) - a TrackSet is used as is."""
+def _open(all_tracks, dt, input_LocErr, device, gaps=False):
+    """(TrackSet, owned, bucket keys) - a TrackSet is used as is (a gapped one included); ``gaps``: the dict's all-NaN rows are missed detections."""
     if isinstance(all_tracks, engine.TrackSet):
         ts, owned, keys = all_tracks, False, None
     else:
         if isinstance(dt, (dict, list)):
             raise NotImplementedError("per-track scores with per-track time steps are not built (the fixed-window kernels take a scalar dt)")
         _, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
-        ts, owned = engine.TrackSet(tracks, sigmas, device=0 if device is None else int(device)), True
+        ts, owned = engine.TrackSet(tracks, sigmas, device=0 if device is None else int(device), gaps=gaps), True
         keys = [str(t.shape[1]) for t in tracks]
     if ts.has_dt:
         if owned:
@@ -202,17 +202,21 @@ def _scores_call(params, names, ts, dt, cell_dims, nb_states, nb_substeps, frame
     if model is None:
         return None
     tang = gradient.model_tangents(params, dt, nb_substeps, Matrix_type, cell_dims, names, has_sigma=ts.has_sigma)
+    if ts.gaps:  # the gap-aware forward-mode kernels (extrack_loglik_scores_gaps)
+        return ts.ctx.loglik_scores(model, tang, scores=scores, gaps=True)
     return ts.ctx.loglik_scores(model, tang, scores=scores)
 
 
 def track_scores(all_tracks, dt, params, nb_states=2, nb_substeps=1, frame_len=6, cell_dims=[1], input_LocErr=None, Matrix_type=1,
-                 device=None):
+                 device=None, gaps=False):
     """{str(len): ndarray [n_tracks, p]}: every track's d LL_n / d (value of the free parameter), columns in the order of
     ``gradient.free_names(params)``, rows in the order of the bucket.  The chain rule from the parameters to the model goes through
-    ``gradient.model_tangents``, the recursion through the forward-mode gradient kernels (extrack_loglik_scores)."""
+    ``gradient.model_tangents``, the recursion through the forward-mode gradient kernels (extrack_loglik_scores).
+    ``gaps``: all-NaN rows of the track dict are missed detections (``extrack_amd.gaps``; extrack_loglik_scores_gaps); a gapped
+    ``TrackSet`` is used as it is."""
     params = _own(params)
     names = gradient.free_names(params)
-    ts, owned, keys = _open(all_tracks, dt, input_LocErr, device)
+    ts, owned, keys = _open(all_tracks, dt, input_LocErr, device, gaps)
     try:
         if keys is None:
             keys = [str(s[1]) for s in ts.shapes]
@@ -230,7 +234,7 @@ def track_scores(all_tracks, dt, params, nb_states=2, nb_substeps=1, frame_len=6
 
 
 def parameter_uncertainties(all_tracks, dt, params, nb_states=2, nb_substeps=1, frame_len=6, cell_dims=[1], input_LocErr=None,
-                            Matrix_type=1, device=None, method="opg", comm=None):
+                            Matrix_type=1, device=None, method="opg", comm=None, gaps=False):
     """Covariance and standard errors of the fitted ``params`` (see the module docstring for the three methods, the refusal rules and
     the treatment of bounds and ``expr`` parameters).  ``all_tracks``: the track dict, or a ``TrackSet`` (with ``comm``: this rank's
     shard - every rank evaluates its own tracks, the p x p matrix and the (1 + p) vector {sum LL, gradient} are summed with
@@ -238,12 +242,17 @@ def parameter_uncertainties(all_tracks, dt, params, nb_states=2, nb_substeps=1, 
     {name: float | None}, correl, opg, hessian (None when the method does not need it), method, message, loglik, gradient.
 
     Hessian: central differences of ``gradient.objective_and_gradient`` with the steps of ``hessian_steps`` (1e-4 of the value, at
-    most half the distance to the nearer bound), symmetrised."""
+    most half the distance to the nearer bound), symmetrised.
+
+    ``gaps``: all-NaN rows of the track dict are missed detections (a gapped ``TrackSet`` is used as it is): scores and gradient come from
+    the gap-aware forward-mode kernels, all three methods work; one GPU only (``comm`` raises NotImplementedError)."""
     if method not in METHODS:
         raise ValueError("method must be one of %s" % (METHODS,))
+    if comm is not None and (gaps or (isinstance(all_tracks, engine.TrackSet) and all_tracks.gaps)):
+        raise NotImplementedError("missed detections (gaps=True) are not built for distributed evaluation: comm must be None")
     params = _own(params)
     kept, dropped = split_on_bounds(params)
-    ts, owned, _ = _open(all_tracks, dt, input_LocErr, device)
+    ts, owned, _ = _open(all_tracks, dt, input_LocErr, device, gaps)
     try:
         B = H = ll = g = None
         p = len(kept)

@@ -49,6 +49,9 @@
  *       extrack_loglik AND its exact gradient in one pass.  It replaces the finite-difference loop that the reference's
  *       optimiser runs around cum_Proba_Cs (lmfit.minimize at extrack/tracking.py:1371: BFGS evaluates the objective
  *       nvar + 1 times per iteration to difference it numerically).
+ *   extrack_loglik_grad_gaps / extrack_loglik_scores_gaps
+ *       extrack_loglik_grad / extrack_loglik_scores for tracks with missed detections (all-NaN rows, as extrack_loglik_gaps): nothing in
+ *       the reference.
  *   extrack_loglik_scores
  *       the same evaluation keeping every track's own dLL_n/dtheta and their outer-product sum: what the parameter standard errors
  *       of a fit are computed from (the reference returns point estimates only).
@@ -277,6 +280,27 @@ int extrack_loglik_scores(extrack_ctx* ctx, const extrack_model* model, int32_t 
  * row-major} in stream order - a multi-GPU caller all-reduces that buffer; the scores themselves are never gathered. */
 int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
                                 double* d_out);
+/* extrack_loglik_grad / extrack_loglik_scores (and their _async forms) for tracks with missed detections: all-NaN rows as
+ * extrack_loglik_gaps defines them, same arguments and outputs as the plain calls.  At a gap step the merged state and its tangents go
+ * through the transition alone (rz' = R + d log T[q], dm' = d m_bar, du' = d d2_q + d u_bar): no Gaussian factor, and neither the
+ * position nor the per-peak error of the row is read (the error may be NaN).  total_ll is the value extrack_loglik_gaps returns; its
+ * + n_gaps * dims / 2 * log(2 pi) per track does not depend on the model and adds nothing to gradient and scores.  A NaN first or last
+ * row, a row with only some NaN coordinates or a NaN error at an observed row gives the track a NaN LL and NaN scores.  Served by
+ * gap-aware instantiations of the two forward-mode bodies (csrc/extrack_grad_gaps.hip): csrc/xt_gradr.h for up to 256 groups of
+ * sequences per track, else csrc/xt_grad.h for up to 1024; the register-resident 2-state kernels and the reverse-mode kernels have no
+ * gap-aware variant and are bypassed.  Decided on the host before anything is enqueued, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2,
+ * n_states > 4, buckets with per-track time steps, models that fit neither kernel.  n_dir == 0 is extrack_loglik_gaps (for the _async
+ * form: evaluated synchronously, the sum then copied to d_out).  Scores: rows in bucket-upload order, ONE launch group, opg as in
+ * extrack_loglik_scores.  Gap-free data gives the values of the plain calls up to the rounding of another kernel family (two states: the
+ * plain call runs csrc/xt_reg2.h).  extrack_last_grad_ms / extrack_last_launch_info cover the launches. */
+int extrack_loglik_grad_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                             double* total_ll, double* grad);
+int extrack_loglik_grad_gaps_async(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                                   double* d_out);
+int extrack_loglik_scores_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                               double* total_ll, double* grad, double* opg, double* scores);
+int extrack_loglik_scores_gaps_async(extrack_ctx* ctx, const extrack_model* model, int32_t n_dir, const extrack_model_tangent* tangents,
+                                     double* d_out);
 /* Device time (ms) of the gradient kernels of the last extrack_loglik_grad / extrack_loglik_th_grad (or _async) call (waits for them). */
 int extrack_last_grad_ms(extrack_ctx* ctx, float* ms);
 
