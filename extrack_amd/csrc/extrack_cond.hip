@@ -93,16 +93,10 @@ int xt_refine_fixed_states_launch(extrack_ctx* ctx, const extrack_model* m, int3
     }
 
     XT_HIP(ctx, hipSetDevice(ctx->device));
-    auto key = std::make_pair(kp, std::make_pair(threads, lds));
-    auto it = ctx->occ_cache.find(key);
-    // at every launch, not only on a cache miss: the attribute belongs to the kernel, and a smaller request in between would leave it low
+    // at every launch, not only when the occupancy is first asked for: the attribute belongs to the kernel, and a smaller request in between would leave it low
     if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if (it == ctx->occ_cache.end()) {
-        int occ = 0;
-        XT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, threads, lds));
-        it = ctx->occ_cache.emplace(key, occ < 1 ? 1 : occ).first;
-    }
-    const int occ = it->second;
+    int occ = 0;
+    XT_HIP(ctx, xt_occupancy(ctx, kp, threads, lds, &occ));
     const int64_t nbatch = (b.N + tpb - 1) / tpb;
     // one block per batch of 64 tracks: the blocks are independent and cheap to start, so the hardware balances them; beyond 2^20 blocks
     // (or with EXTRACK_COND_MAX_BLOCKS, for tests) a block walks several batches
@@ -146,12 +140,7 @@ int xt_refine_fixed_states_launch(extrack_ctx* ctx, const extrack_model* m, int3
     XT_HIP(ctx, hipMemcpyAsync(sigma, a.sig_out, sg_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (logdens) XT_HIP(ctx, hipMemcpyAsync(logdens, a.logdens, ld_bytes, hipMemcpyDeviceToHost, ctx->stream));
     XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->launch_info[0] = grid;
-    ctx->launch_info[1] = threads;
-    ctx->launch_info[2] = (int32_t)lds;
-    ctx->launch_info[3] = tpb;
-    ctx->launch_info[4] = occ;
-    ctx->launch_info[5] = ctx->n_cu;
+    xt_set_launch_info(ctx, grid, threads, lds, tpb, occ);
     return EXTRACK_OK;
 }
 

@@ -68,127 +68,30 @@ void xt_grad_reduce_launch(hipStream_t st, const double* partials, int nrows, in
     hipLaunchKernelGGL(xt_grad_reduce, dim3(ncol), dim3(256), 0, st, partials, nrows, ncol, ll_dst, out, d);
 }
 
-struct GradLauncher {
-    extrack_ctx* ctx;
-    XtKernelArgs a;
-    XtGradArgs ga;
-    int threads = 0;
-    size_t lds = 0;
-    int grid = 0;
-    hipError_t herr = hipSuccess;
-
-    template <int G_, int D, int K>
-    bool run()
-    {
-        if (threads <= 256) return launch(xt_grad_kernel<G_, D, K, 256>);
-        return launch(xt_grad_kernel<G_, D, K, 1024>);
-    }
-    // the gap-aware instantiations live in extrack_grad_gaps.hip: launched through their address
-    bool run_gaps(int G, int D, int K)
-    {
-        const void* kp = xt_grad_gap_kernel_ptr(G, D, K, threads > 256);
-        if (!kp) return false;
-        if (lds > 64 * 1024) {
-            herr = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (herr != hipSuccess) return true;
-        }
-        void* kargs[2] = {(void*)&a, (void*)&ga};
-        herr = hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream);
-        return true;
-    }
-    template <class KernT>
-    bool launch(KernT kern)
-    {
-        if (lds > 64 * 1024) {
-            herr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (herr != hipSuccess) return true;
-        }
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, ctx->stream, a, ga);
-        herr = hipGetLastError();
-        return true;
-    }
-};
-
-template <int GG, class L>
-static bool xt_grad_dispatch_dk(int D, int K, L& l)
+template <int G_>
+static const void* grad_dk(int D, int K, bool wide)
 {
-    if (D == 1 && K == 1) return l.template run<GG, 1, 1>();
-    if (D == 2 && K == 1) return l.template run<GG, 2, 1>();
-    if (D == 2 && K == 2) return l.template run<GG, 2, 2>();
-    if (D == 3 && K == 1) return l.template run<GG, 3, 1>();
-    if (D == 3 && K == 3) return l.template run<GG, 3, 3>();
-    return false;
+#define XT_GK(DD, KK) (wide ? (const void*)xt_grad_kernel<G_, DD, KK, 1024> : (const void*)xt_grad_kernel<G_, DD, KK, 256>)
+    if (D == 1 && K == 1) return XT_GK(1, 1);
+    if (D == 2 && K == 1) return XT_GK(2, 1);
+    if (D == 2 && K == 2) return XT_GK(2, 2);
+    if (D == 3 && K == 1) return XT_GK(3, 1);
+    if (D == 3 && K == 3) return XT_GK(3, 3);
+#undef XT_GK
+    return nullptr;
 }
-
-template <class L>
-static bool xt_grad_dispatch(int G, int D, int K, L& l)
+// The LDS-resident kernel; G outside 2 .. 4: the generic instantiation.  wide: more than 256 threads.  Built where xt_grad_lds_built(gaps = false) holds.
+static const void* xt_grad_kernel_ptr(int G, int D, int K, bool wide)
 {
-    if (G == 2) return xt_grad_dispatch_dk<2>(D, K, l);
-    if (G == 3) return xt_grad_dispatch_dk<3>(D, K, l);
-    if (G == 4) return xt_grad_dispatch_dk<4>(D, K, l);
-    return xt_grad_dispatch_dk<0>(D, K, l);
-}
-
-// LDS bytes of a block of tpb tracks with NP directions
-static size_t xt_grad_lds_bytes(const XtConfig& c, int D, int K, int NP, int tpb, bool tan_lds)
-{
-    size_t d = (size_t)((xt_tab_doubles(c.S, c.G) + 1) & ~1);
-    if (tan_lds) d += (size_t)((NP * xt_grad_tb_doubles(c.S, c.G) + 1) & ~1);
-    d += (size_t)tpb * ((size_t)xt_grad_region_doubles(c.EP, D, K, NP) + xt_grad_acc_doubles(NP, c.NG) + xt_stage_doubles(D));
-    return d * sizeof(double);
-}
-
-// Geometry of one pass of the LDS-resident kernel (xt_grad.h) with NP directions
-struct XtGradLdsGeom {
-    bool tan_lds;
-    int PJ, tpb, threads;
-    size_t lds;
-};
-static XtGradLdsGeom xt_grad_lds_geometry(const XtConfig& c, int D, int K, int NP)
-{
-    XtGradLdsGeom o;
-    o.tan_lds = (size_t)NP * xt_grad_tb_doubles(c.S, c.G) * 8 <= 16 * 1024;
-    const size_t per_track = xt_grad_lds_bytes(c, D, K, NP, 1, o.tan_lds) - xt_grad_lds_bytes(c, D, K, NP, 0, o.tan_lds);
-    const size_t fixed = xt_grad_lds_bytes(c, D, K, NP, 0, o.tan_lds);
-    const size_t budget = 64 * 1024;
-    // PJ lanes per group: about two directions per lane, as long as a track's threads fit a workgroup
-    int PJ = 1;
-    while (PJ < 8 && PJ * 2 <= NP && NP > 2 * PJ - 1 && c.NG * PJ * 2 <= 1024) PJ *= 2;
-    if (const char* ev = getenv("EXTRACK_GRAD_PJ")) {
-        const int v = atoi(ev);
-        if ((v == 1 || v == 2 || v == 4 || v == 8) && c.NG * v <= 1024) PJ = v;
-    }
-    const int NT = c.NG * PJ;
-    const int by_threads = NT >= 256 ? 1 : 256 / NT;
-    const int by_lds = budget > fixed + per_track ? (int)((budget - fixed) / per_track) : 1;
-    o.PJ = PJ;
-    o.tpb = std::max(1, std::min(by_threads, by_lds));
-    o.threads = (o.tpb * NT + 63) / 64 * 64;
-    o.lds = xt_grad_lds_bytes(c, D, K, NP, o.tpb, o.tan_lds);
-    return o;
-}
-// directions per pass of the LDS-resident kernel: as many as keep one track's state within the LDS of a CU (all of them for the usual models)
-static int xt_grad_lds_npass_dir(const XtConfig& c, int D, int K, int n_dir)
-{
-    int npass_dir = std::max(n_dir, 1);
-    while (npass_dir > 1 && (npass_dir > 16 || xt_grad_lds_bytes(c, D, K, npass_dir, 1, false) > 150 * 1024)) npass_dir = (npass_dir + 1) / 2;
-    return npass_dir;
-}
-// directions per pass (and the compile-time NPC) of the register-resident kernel (xt_gradr.h)
-static int xt_gradr_per_pass(const extrack_ctx* ctx, int n_dir, int* NPC_out)
-{
-    // 4 directions per pass: with 6 the register allocator spills inside the step loop (3 states: 917 GB of scratch traffic per C3
-    // launch, r03 PMC) and the pass count saved does not pay for it; 3 per pass when that needs no more passes
-    int NPC = ctx->gradr_npc ? ctx->gradr_npc : 4;
-    const int npass = (n_dir + NPC - 1) / NPC, per = (n_dir + npass - 1) / npass;
-    if (per <= 3 && !ctx->gradr_npc) NPC = 3;
-    *NPC_out = NPC;
-    return per;
+    if (G == 2) return grad_dk<2>(D, K, wide);
+    if (G == 3) return grad_dk<3>(D, K, wide);
+    if (G == 4) return grad_dk<4>(D, K, wide);
+    return grad_dk<0>(D, K, wide);
 }
 
 // Missed detections (extrack_loglik_grad_gaps / extrack_loglik_scores_gaps): the refusals of extrack_loglik_gaps, decided here on the host
-// before anything is enqueued or recorded - nb_substeps >= 2, more than 4 states, buckets with per-track time steps, and models that fit
-// neither the register-resident nor the LDS-resident gap-aware kernel (extrack_grad_gaps.hip).
+// before anything is enqueued or recorded - nb_substeps >= 2, more than 4 states, buckets with per-track time steps, and models for which
+// xt_grad_pick finds no gap-aware kernel (extrack_grad_gaps.hip).
 static int xt_grad_gaps_check(extrack_ctx* ctx, const extrack_model* m, int n_dir)
 {
     if (m->nb_substeps != 1) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: built for nb_substeps == 1");
@@ -201,20 +104,7 @@ static int xt_grad_gaps_check(extrack_ctx* ctx, const extrack_model* m, int n_di
         const int D = b.D, K = m->locerr_mode == 0 ? m->locerr_dims : b.KS;
         if (K != 1 && K != D) return xt_fail(ctx, EXTRACK_E_INVALID, m->locerr_mode == 0 ? "locerr_dims must be 1 or the track dimensionality"
                                                                                          : "per-peak localisation error mode but the bucket has no sigma");
-        if (ctx->grad_reg2 && c.NG <= 256) {
-            int NPC;
-            const int per = xt_gradr_per_pass(ctx, n_dir, &NPC);
-            if (xt_gradr_gap_kernel_ptr(c.G, D, K, NPC) &&
-                xt_gradr_lds_bytes(c.S, c.G, c.E, c.EP, c.NG, c.P, D, K, per, std::max(1, 256 / c.NG)) <= 160 * 1024)
-                continue;
-        }
-        const int npass_dir = xt_grad_lds_npass_dir(c, D, K, n_dir);
-        bool fits = c.NG <= 1024 && xt_grad_lds_bytes(c, D, K, std::min(npass_dir, n_dir), 1, false) <= 160 * 1024;
-        for (int p0 = 0; fits && p0 < n_dir; p0 += npass_dir) {
-            const XtGradLdsGeom gm = xt_grad_lds_geometry(c, D, K, std::min(npass_dir, n_dir - p0));
-            fits = gm.threads <= 1024 && gm.lds <= 160 * 1024 && xt_grad_gap_kernel_ptr(c.G, D, K, gm.threads > 256) != nullptr;
-        }
-        if (!fits)
+        if (xt_grad_pick(c, D, K, m->locerr_mode, n_dir, b.L, 1, ctx->n_cu, true, false, ctx->grad_knobs).path == XT_GRAD_NONE)
             return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "missed detections: the model fits neither gap-aware gradient kernel (more than 1024 groups of sequences or more than 160 KiB of LDS per track)");
     }
     return EXTRACK_OK;
@@ -232,20 +122,36 @@ static int xt_grad_reserve(extrack_ctx* ctx, double** buf, size_t* cap, size_t n
     return EXTRACK_OK;
 }
 
-// Enqueues the kernels of one likelihood + gradient evaluation on the context's stream; d_out (device, 1 + n_dir doubles) receives
-// {sum LL, d sum LL / d theta_i}.  Nothing waits for the device: passes and launch groups accumulate in stream order.
-// d_scores (device, [sum N][n_dir], or nullptr): a scores evaluation - the forward-mode kernels also store every track's dLL_n/dtheta, rows
-// in bucket-id order, columns in launch order (cols->idx[c] = the caller's direction of column c); the reverse-mode kernels are bypassed
-// (their adjoints are accumulated across tracks) and d_opg (device, [n_dir][n_dir], or nullptr) receives sum_n s_n s_n^T.
-// gaps: tracks with missed detections (all-NaN rows) - the gap-aware instantiations of the two forward-mode bodies only (extrack_grad_gaps.hip:
-// the register-resident 2-state and the reverse-mode kernels have none), the register-resident one first, then the LDS-resident one.
-static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out,
-                           double* d_scores = nullptr, XtOpgCols* cols = nullptr, double* d_opg = nullptr, bool gaps = false)
+// One likelihood + gradient evaluation on the context's stream, through the stages below; nothing waits for the device: passes and launch
+// groups accumulate in stream order.
+//   begin -> per launch group: group_begin -> xt_grad_pick -> xt_grad_rev_launch | xt_grad_run_reg2 | xt_grad_run_passes -> group_done -> OPG, events
+struct XtGradEval {
+    extrack_ctx* ctx;
+    const extrack_model* m;
+    int n_dir, TB;
+    double* d_out;     // device, 1 + n_dir doubles: {sum LL, d sum LL / d theta_i}
+    double* d_scores;  // a scores evaluation (else nullptr): device [sum N][n_dir], every track's dLL_n/dtheta from the forward-mode kernels (reverse mode is
+                       // bypassed: its adjoints are accumulated across tracks); rows in bucket-id order, columns in launch order
+    XtOpgCols* cols;   // cols->idx[c] = the caller's direction of column c
+    bool gaps;         // tracks with missed detections (all-NaN rows): the gap-aware instantiations of the two forward-mode bodies only
+    std::vector<double> blob;  // the model blob on the host
+    // the launch group in hand
+    std::vector<XtBucketDesc> descs;
+    int D, K, KS, group_index = 0;
+    size_t doff, poff = 0;  // its descriptors in ctx->d_desc; the free rows of ctx->d_gpartials start here
+    double* g_out;          // d_out for the first group; the later ones write a scratch row that group_done adds to d_out
+};
+
+// validate, config, model blob, tangent blocks into the pinned staging buffer, copy
+static int xt_grad_begin(XtGradEval& ev, const extrack_model_tangent* tangents)
 {
+    extrack_ctx* ctx = ev.ctx;
+    const extrack_model* m = ev.m;
+    const int n_dir = ev.n_dir;
     int rc = xt_validate_model(ctx, m);
     if (rc) return rc;
     if (ctx->buckets.empty()) return xt_fail(ctx, EXTRACK_E_INVALID, "no bucket uploaded");
-    if (gaps && (rc = xt_grad_gaps_check(ctx, m, n_dir))) return rc;
+    if (ev.gaps && (rc = xt_grad_gaps_check(ctx, m, n_dir))) return rc;
     for (int i = 0; i < n_dir; ++i)
         if (!tangents[i].ds2 || !tangents[i].Fs || !tangents[i].TrMat || !tangents[i].p_stay)
             return xt_fail(ctx, EXTRACK_E_INVALID, "null tangent field");
@@ -254,10 +160,9 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
     const XtConfig& c = ctx->cfg;
     XtModelHost mh;
     xt_model_host(m, mh);
-    std::vector<double> blob;
-    xt_build_blob(mh, c, blob);
-    if ((rc = xt_upload_blob(ctx, blob))) return rc;
-    const int TB = xt_grad_tb_doubles(c.S, c.G);
+    xt_build_blob(mh, c, ev.blob);
+    if ((rc = xt_upload_blob(ctx, ev.blob))) return rc;
+    const int TB = ev.TB = xt_grad_tb_doubles(c.S, c.G);
     // tangent tables: built in a pinned staging buffer the asynchronous copy reads from; an event guards its reuse by the next call
     const size_t ndbl = (size_t)std::max(n_dir, 1) * TB;
     if (ctx->dblob_busy) {
@@ -277,376 +182,282 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
     XT_HIP(ctx, hipMemcpyAsync(ctx->d_dblob, ctx->h_dblob, ndbl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     XT_HIP(ctx, hipEventRecord(ctx->ev_dblob, ctx->stream));
     ctx->dblob_busy = true;
+    return EXTRACK_OK;
+}
 
-    // launch groups: buckets with the same (dims, sigma dims), longest first
-    std::vector<XtBucket*> order;
-    for (auto& b : ctx->buckets) order.push_back(&b);
-    std::stable_sort(order.begin(), order.end(), [](const XtBucket* x, const XtBucket* y) {
-        if (x->D != y->D) return x->D < y->D;
-        if (x->KS != y->KS) return x->KS < y->KS;
-        return x->L > y->L;
-    });
-    std::vector<std::vector<XtBucket*>> groups;
-    for (XtBucket* b : order) {
-        if (groups.empty() || groups.back().size() >= XT_MAX_BUCKETS || groups.back()[0]->D != b->D || groups.back()[0]->KS != b->KS)
-            groups.emplace_back();
-        groups.back().push_back(b);
+// dims of the group, its bucket descriptors (shared by its passes) -> device
+static int xt_grad_group_begin(XtGradEval& ev, const std::vector<XtBucket*>& g)
+{
+    extrack_ctx* ctx = ev.ctx;
+    const extrack_model* m = ev.m;
+    ev.g_out = ev.group_index == 0 ? ev.d_out : ctx->d_gtmp;
+    ev.poff = 0;  // the previous group's reductions precede this group's kernels in the stream: the partial-sum rows are free again
+    const XtBucket& b0 = *g[0];
+    ev.D = b0.D;
+    ev.KS = b0.KS ? b0.KS : 1;
+    if (m->locerr_mode == 0) {
+        ev.K = m->locerr_dims;
+        if (ev.K != 1 && ev.K != ev.D) return xt_fail(ctx, EXTRACK_E_INVALID, "locerr_dims must be 1 or the track dimensionality");
+    } else {
+        if (!b0.d_sigma) return xt_fail(ctx, EXTRACK_E_INVALID, "per-peak localisation error mode but the bucket has no sigma");
+        ev.K = b0.KS;
     }
-    if (order.size() > (size_t)XT_DESC_CAP / 2) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "too many buckets");
+    ev.descs.clear();
+    for (XtBucket* b : g) {
+        XtBucketDesc d;
+        d.tracks = b->d_tracks;
+        d.sigma = m->locerr_mode ? b->d_sigma : nullptr;
+        d.ll_out = nullptr;
+        d.preds_out = nullptr;
+        d.N = b->N;
+        d.L = b->L;
+        d.isBL = (b->L != m->max_len) ? 1 : 0;  // tracking.py:1037-1040
+        d.ll_const = -(double)(b->L - 1) * ev.D * 0.5 * XT_LOG2PI;
+        if (ev.d_scores) {  // rows of the buckets uploaded before this one come first (the order of extrack_loglik's per_track)
+            int64_t row0 = 0;
+            for (const XtBucket* o = ctx->buckets.data(); o != b; ++o) row0 += o->N;
+            d.scores_out = ev.d_scores + row0 * ev.n_dir;
+        }
+        ev.descs.push_back(d);
+    }
+    ctx->desc_shadow.clear();  // this path writes the device table itself: the likelihood launcher's shadow of it no longer holds
+    memcpy(ctx->h_desc + ev.doff, ev.descs.data(), ev.descs.size() * sizeof(XtBucketDesc));
+    XT_HIP(ctx, hipMemcpyAsync(ctx->d_desc + ev.doff, ctx->h_desc + ev.doff, ev.descs.size() * sizeof(XtBucketDesc), hipMemcpyHostToDevice, ctx->stream));
+    XT_HIP(ctx, hipEventRecord(ctx->ev_blob[(ctx->blob_turn - 1u) & 1u], ctx->stream));
+    return EXTRACK_OK;
+}
+
+// the kernel arguments every family shares
+static void xt_grad_common_args(const XtGradEval& ev, int tpb, XtKernelArgs& a)
+{
+    extrack_ctx* ctx = ev.ctx;
+    a.desc = ctx->d_desc + ev.doff;
+    a.ndesc = (int32_t)ev.descs.size();
+    a.blob = ctx->d_blob;
+    a.base_tab = ctx->d_base_tab;
+    a.off_tab = ctx->d_off_tab;
+    a.TPB = tpb;
+    a.min_len = ev.m->min_len;
+    a.locerr_mode = ev.m->locerr_mode;
+    a.KS = ev.KS;
+}
+
+// One pass of a forward-mode family (reg2, gradr, lds): NP directions from dblob (+ NU uniform ones, reg2) through kernel kp, then the
+// column sums of its per-block partials -> g_out (column 1 + i -> direction dst.idx[i]; sum LL from the first pass only).
+struct XtGradPass {
+    const void* kp;
+    int threads, tpb;
+    size_t lds;
+    int oversub;    // block generations per CU
+    bool est_occ;   // workgroups per CU from the LDS and thread budget of a CU instead of the device query (lds)
+    const double* dblob;
+    int p0, NP, NU = 0;
+    int tan_lds = 0, PJ = 0;  // lds
+    bool r2 = false;          // reg2: one global localisation error, no digit tables; udblob / score_ucol0 follow the NF full directions
+    int NF = 0, well_scaled = 0;
+    XtGradDst dst;
+};
+static int xt_grad_pass(XtGradEval& ev, const XtGradPass& p)
+{
+    extrack_ctx* ctx = ev.ctx;
+    if (!p.kp) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
+    int occ = 0;
+    if (p.est_occ) {  // the LDS-resident kernel: its dynamic-LDS limit follows the pass
+        if (p.lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(p.kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+        occ = std::max(1, std::min((int)((160 * 1024) / p.lds), 2048 / p.threads));
+    } else XT_HIP(ctx, xt_occupancy(ctx, p.kp, p.threads, p.lds, &occ));
+    XtKernelArgs a;
+    memset(&a, 0, sizeof(a));
+    xt_fill_args_from_config(ctx->cfg, a);
+    XtGradArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    // grid: blocks per bucket in proportion to its work, CUs oversubscribed (as the likelihood launcher does); at most as many blocks as
+    // the free part of the partial-sum buffer has rows
+    const int ncol = p.NP + p.NU + 1;
+    const int64_t sg = xt_split_descs((double)occ * ctx->n_cu * p.oversub, (int64_t)((ctx->gpartials_cap - ev.poff) / ncol), ev.descs, p.tpb, a.blk_end);
+    if (sg < 0 || ev.poff + (size_t)sg * ncol > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
+    const int grid = (int)sg;
+    xt_grad_common_args(ev, p.tpb, a);
+    ga.dblob = p.dblob;
+    ga.gpartials = ctx->d_gpartials + ev.poff;
+    ga.NP = p.NP, ga.TB = ev.TB, ga.tan_lds = p.tan_lds, ga.PJ = p.PJ;
+    ga.score_ld = ev.n_dir, ga.score_col0 = p.p0;
+    if (p.r2) {
+        a.base_tab = a.off_tab = nullptr;
+        a.locerr_mode = 0, a.KS = 1, a.well_scaled = p.well_scaled;
+        ga.NU = p.NU, ga.score_ucol0 = p.NF;
+        ga.udblob = ctx->d_dblob2 + (size_t)p.NF * ev.TB;
+    }
+    void* kargs[2] = {(void*)&a, (void*)&ga};
+    const hipError_t e = hipLaunchKernel(p.kp, dim3(grid), dim3(p.threads), kargs, p.lds, ctx->stream);
+    if (e != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("gradient kernel launch: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(xt_grad_reduce, dim3(ncol), dim3(256), 0, ctx->stream, ctx->d_gpartials + ev.poff, grid, ncol, p.p0 == 0 ? ev.g_out : nullptr,
+                       ev.g_out + 1, p.dst);
+    XT_HIP(ctx, hipGetLastError());
+    ev.poff += (size_t)grid * ncol;
+    xt_set_launch_info(ctx, grid, p.threads, p.lds, p.tpb, occ);
+    return EXTRACK_OK;
+}
+
+// reverse mode (xt_rev.h): one launch whatever the number of directions, one log region per track slot of every block, then the projection
+static int xt_grad_rev_launch(XtGradEval& ev, const XtGradPick& pk)
+{
+    extrack_ctx* ctx = ev.ctx;
+    const XtConfig& c = ctx->cfg;
+    const int TB = ev.TB, tpb = pk.tpb;
+    const void* kp = xt_rev_kernel_ptr(c.G, ev.D, ev.K, pk.nbuf);
+    if (!kp) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
+    if (pk.lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
+    int occ = 0, rc;
+    XT_HIP(ctx, xt_occupancy(ctx, kp, pk.threads, pk.lds, &occ));
+    XtKernelArgs a;
+    memset(&a, 0, sizeof(a));
+    xt_fill_args_from_config(c, a);
+    XtRevArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    const double target = std::min((double)occ * ctx->n_cu * ctx->grad_knobs.rev_oversub, (double)pk.max_blocks);
+    // at most max_blocks log regions: the budget holds for the launched grid, not only for the target
+    const int64_t sg = xt_split_descs(target, (int64_t)std::min<size_t>(pk.max_blocks, INT64_MAX), ev.descs, tpb, a.blk_end);
+    if (sg < 0) return xt_fail(ctx, EXTRACK_E_INVALID, "reverse-mode gradient: no grid split within the log budget");
+    const int grid = (int)sg;
+    ra.TB = TB, ra.log_stride = pk.log_stride;
+    if ((rc = xt_grad_reserve(ctx, &ctx->d_revlog, &ctx->revlog_cap, (size_t)grid * tpb * (size_t)ra.log_stride))) return rc;
+    if ((rc = xt_grad_reserve(ctx, &ctx->d_revadj, &ctx->revadj_cap, (size_t)TB))) return rc;
+    if ((rc = xt_grad_reserve(ctx, &ctx->d_gpartials, &ctx->gpartials_cap, ev.poff + (size_t)grid * (TB + 1)))) return rc;
+    xt_grad_common_args(ev, tpb, a);
+    a.base_tab = a.off_tab = nullptr;
+    ra.gpartials = ctx->d_gpartials + ev.poff, ra.log = ctx->d_revlog;
+    void* kargs[2] = {(void*)&a, (void*)&ra};
+    XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(pk.threads), kargs, pk.lds, ctx->stream));
+    hipLaunchKernelGGL(xt_grad_reduce, dim3(TB + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + ev.poff, grid, TB + 1, ev.g_out, ctx->d_revadj,
+                       xt_grad_dst_identity(0));
+    XT_HIP(ctx, hipGetLastError());
+    xt_rev_project(ctx->stream, ctx->d_revadj, ctx->d_dblob, TB, ev.n_dir, ev.g_out + 1);
+    XT_HIP(ctx, hipGetLastError());
+    ev.poff += (size_t)grid * (TB + 1);
+    xt_set_launch_info(ctx, grid, pk.threads, pk.lds, tpb, occ);
+    return EXTRACK_OK;
+}
+
+// two-state models: register-resident kernels (xt_reg2.h), <= 8 directions per pass, tangents in VGPRs
+static int xt_grad_run_reg2(XtGradEval& ev, const XtGradPick& pk)
+{
+    extrack_ctx* ctx = ev.ctx;
+    const extrack_model* m = ev.m;
+    const int n_dir = ev.n_dir, TB = ev.TB;
+    // "uniform" directions (xt_r2_uniform_direction, e.g. pBL) cost no per-step work: they ride along with the first pass
+    std::vector<int> full, uni;
+    for (int i = 0; i < n_dir; ++i)
+        ((int)uni.size() < XT_R2_MAXU && xt_r2_uniform_direction(ctx->h_dblob + (size_t)i * TB) ? uni : full).push_back(i);
+    if (full.empty()) {
+        full.push_back(uni.back());
+        uni.pop_back();
+    }
+    // device copy of the tangent blocks in launch order: full directions first, then the uniform ones
+    const int NF = (int)full.size(), NUn = (int)uni.size();
+    int rc = xt_grad_reserve(ctx, &ctx->d_dblob2, &ctx->dblob2_cap, (size_t)n_dir * TB);
+    if (rc) return rc;
+    for (int i = 0; i < n_dir; ++i) {
+        const int src = i < NF ? full[i] : uni[i - NF];
+        XT_HIP(ctx, hipMemcpyAsync(ctx->d_dblob2 + (size_t)i * TB, ctx->d_dblob + (size_t)src * TB, (size_t)TB * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    const int npass = (NF + pk.maxnp - 1) / pk.maxnp, per = (NF + npass - 1) / npass;
+    if (ev.d_scores)
+        for (int i = 0; i < n_dir; ++i) ev.cols->idx[i] = i < NF ? full[i] : uni[i - NF];
+    double lo = INFINITY, hi = -INFINITY;
+    for (int k = 0; k < m->locerr_dims && k < 3; ++k) {
+        lo = std::min(lo, m->locerr[k] * m->locerr[k]);
+        hi = std::max(hi, m->locerr[k] * m->locerr[k]);
+    }
+    XtGradPass p = {};
+    p.threads = pk.threads, p.tpb = pk.tpb, p.oversub = ctx->grad_knobs.oversub, p.r2 = true, p.NF = NF;
+    p.well_scaled = xt_model_well_scaled(ev.blob, lo, hi) ? 1 : 0;
+    for (int p0 = 0; p0 < NF && !rc; p0 += per) {
+        p.p0 = p0, p.NP = std::min(per, NF - p0), p.NU = p0 == 0 ? NUn : 0;
+        p.kp = xt_r2_kernel(ctx->cfg.F, ev.D, ev.K, p.NP);
+        p.lds = (size_t)xt_r2_block_bytes(p.NP + p.NU, ev.D, 0, pk.tpw);
+        p.dblob = ctx->d_dblob2 + (size_t)p0 * TB;
+        p.dst = xt_grad_dst_identity(0);  // column 1 + i of this launch -> the caller's direction index
+        for (int i = 0; i < p.NP; ++i) p.dst.idx[i] = full[p0 + i];
+        for (int i = 0; i < p.NU; ++i) p.dst.idx[p.NP + i] = uni[i];
+        rc = xt_grad_pass(ev, p);
+    }
+    return rc;
+}
+
+// the forward-mode families with the directions in the caller's order: register + LDS exchange (xt_gradr.h: passes of pk.per directions)
+// and LDS-resident (xt_grad.h: passes of pk.npass_dir directions, the geometry is that of the pass)
+static int xt_grad_run_passes(XtGradEval& ev, const XtGradPick& pk)
+{
+    extrack_ctx* ctx = ev.ctx;
+    const int G = ctx->cfg.G, D = ev.D, K = ev.K, n_dir = ev.n_dir;
+    const bool gradr = pk.path == XT_GRAD_GRADR;
+    const int step = gradr ? pk.per : pk.npass_dir;
+    XtGradPass p = {};
+    p.oversub = 4, p.est_occ = !gradr;
+    if (gradr) {
+        p.kp = ev.gaps ? xt_gradr_gap_kernel_ptr(G, D, K, pk.NPC) : xt_gradr_kernel_ptr(G, D, K, pk.NPC);
+        p.threads = pk.threads, p.tpb = pk.tpb, p.lds = pk.lds;
+        if (p.kp && p.lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(p.kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));  // once for all passes
+    }
+    for (int p0 = 0, rc; p0 < n_dir; p0 += step) {
+        p.p0 = p0, p.NP = std::min(step, n_dir - p0);
+        if (!gradr) {
+            const XtGradLdsGeom& gm = pk.gm[p.NP == pk.rem ? 1 : 0];
+            p.threads = gm.threads, p.tpb = gm.tpb, p.lds = gm.lds, p.tan_lds = gm.tan_lds ? 1 : 0, p.PJ = gm.PJ;
+            p.kp = ev.gaps ? xt_grad_gap_kernel_ptr(G, D, K, gm.threads > 256) : xt_grad_kernel_ptr(G, D, K, gm.threads > 256);
+        }
+        p.dblob = ctx->d_dblob + (size_t)p0 * ev.TB;
+        p.dst = xt_grad_dst_identity(p0);
+        if ((rc = xt_grad_pass(ev, p))) return rc;
+    }
+    return EXTRACK_OK;
+}
+
+// more than one launch group (more than XT_MAX_BUCKETS track lengths, or buckets of different layouts): the groups after the first left
+// {sum LL, gradient} in a scratch row that is added to d_out in stream order
+static void xt_grad_group_done(XtGradEval& ev, size_t nbuckets)
+{
+    if (ev.group_index > 0) hipLaunchKernelGGL(xt_grad_add_kernel, dim3(1), dim3(64), 0, ev.ctx->stream, ev.d_out, ev.ctx->d_gtmp, ev.n_dir + 1);
+    ++ev.group_index;
+    ev.doff += nbuckets;
+}
+
+// Enqueues the kernels of one likelihood + gradient evaluation on the context's stream; d_out (device, 1 + n_dir doubles) receives
+// {sum LL, d sum LL / d theta_i}; scores evaluation: d_scores, cols as in XtGradEval, d_opg (device, [n_dir][n_dir], or nullptr) receives
+// sum_n s_n s_n^T.
+static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_dir, const extrack_model_tangent* tangents, double* d_out,
+                           double* d_scores = nullptr, XtOpgCols* cols = nullptr, double* d_opg = nullptr, bool gaps = false)
+{
+    XtGradEval ev = {ctx, m, n_dir, 0, d_out, d_scores, cols, gaps};
+    int rc = xt_grad_begin(ev, tangents);
+    if (rc) return rc;
+    const std::vector<std::vector<XtBucket*>> groups = xt_launch_groups(ctx, XT_MAX_BUCKETS);
+    if (ctx->buckets.size() > (size_t)XT_DESC_CAP / 2) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "too many buckets");
     if (d_scores && groups.size() > 1)
         return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "per-track scores: buckets of different layouts or more than 64 track lengths");
     int64_t n_total = 0;
     for (auto& b : ctx->buckets) n_total += b.N;
     if (d_scores)
         for (int i = 0; i < XT_OPG_MAXDIR; ++i) cols->idx[i] = i;
-
-    // more than one launch group (more than XT_MAX_BUCKETS track lengths, or buckets of different layouts): the groups after the first write
-    // {sum LL, gradient} to a scratch row that is added to d_out in stream order
-    double* const d_out_final = d_out;
     if (groups.size() > 1 && (rc = xt_grad_reserve(ctx, &ctx->d_gtmp, &ctx->gtmp_cap, (size_t)n_dir + 1))) return rc;
-    int group_index = 0;
-    size_t doff = xt_desc_base(ctx);
-    // per-block partial sums of every pass of the evaluation, one after the other (a pass has at most 32 blocks per CU)
-    size_t poff = 0;
+    ev.doff = xt_desc_base(ctx);
+    // per-block partial sums of every pass of a group, one after the other (a pass has at most 32 blocks per CU)
     if ((rc = xt_grad_reserve(ctx, &ctx->d_gpartials, &ctx->gpartials_cap, ((size_t)ctx->n_cu * 32 * 4 + XT_MAX_BUCKETS) * ((size_t)n_dir + 16)))) return rc;
     if (!ctx->evg0) XT_HIP(ctx, hipEventCreate(&ctx->evg0));
     if (!ctx->evg1) XT_HIP(ctx, hipEventCreate(&ctx->evg1));
     XT_HIP(ctx, hipEventRecord(ctx->evg0, ctx->stream));
-    for (auto& g : groups) {
-        double* const d_out = group_index == 0 ? d_out_final : ctx->d_gtmp;  // (shadows the parameter inside the loop)
-        poff = 0;  // the previous group's reductions precede this group's kernels in the stream: the partial-sum rows are free again
-        auto group_done = [&]() {
-            if (group_index > 0) hipLaunchKernelGGL(xt_grad_add_kernel, dim3(1), dim3(64), 0, ctx->stream, d_out_final, ctx->d_gtmp, n_dir + 1);
-            ++group_index;
-        };
-        const XtBucket& b0 = *g[0];
-        const int D = b0.D;
-        int K;
-        if (m->locerr_mode == 0) {
-            K = m->locerr_dims;
-            if (K != 1 && K != D) return xt_fail(ctx, EXTRACK_E_INVALID, "locerr_dims must be 1 or the track dimensionality");
-        } else {
-            if (!b0.d_sigma) return xt_fail(ctx, EXTRACK_E_INVALID, "per-peak localisation error mode but the bucket has no sigma");
-            K = b0.KS;
-        }
-        const int npass_dir = xt_grad_lds_npass_dir(c, D, K, n_dir);
-        // bucket descriptors of this group (shared by its passes)
-        std::vector<XtBucketDesc> descs;
-        for (XtBucket* b : g) {
-            XtBucketDesc d;
-            d.tracks = b->d_tracks;
-            d.sigma = m->locerr_mode ? b->d_sigma : nullptr;
-            d.ll_out = nullptr;
-            d.preds_out = nullptr;
-            d.N = b->N;
-            d.L = b->L;
-            d.isBL = (b->L != m->max_len) ? 1 : 0;  // tracking.py:1037-1040
-            d.ll_const = -(double)(b->L - 1) * D * 0.5 * XT_LOG2PI;
-            if (d_scores) {  // rows of the buckets uploaded before this one come first (the order of extrack_loglik's per_track)
-                int64_t row0 = 0;
-                for (const XtBucket* o = ctx->buckets.data(); o != b; ++o) row0 += o->N;
-                d.scores_out = d_scores + row0 * n_dir;
-            }
-            descs.push_back(d);
-        }
-        ctx->desc_shadow.clear();  // this path writes the device table itself: the likelihood launcher's shadow of it no longer holds
-        memcpy(ctx->h_desc + doff, descs.data(), descs.size() * sizeof(XtBucketDesc));
-        XT_HIP(ctx, hipMemcpyAsync(ctx->d_desc + doff, ctx->h_desc + doff, descs.size() * sizeof(XtBucketDesc), hipMemcpyHostToDevice, ctx->stream));
-        XT_HIP(ctx, hipEventRecord(ctx->ev_blob[(ctx->blob_turn - 1u) & 1u], ctx->stream));
-        // ---- two-state models: register-resident kernels (xt_reg2.h), <= 8 directions per pass, tangents in VGPRs
-        const bool r2 = !gaps && ctx->grad_reg2 == 1 && xt_use_reg2(c.S, c.NS, c.F) && m->locerr_mode == 0 && n_dir > 0 && xt_r2_kernel(c.F, D, K, 1) != nullptr;
-        // ---- reverse mode (xt_rev.h): one forward + one backward sweep whatever the number of directions; the adjoint of the model blob
-        // is contracted with the tangent blocks by a small kernel.  3 / 4 members per group by default (r03: C3, 13 directions)
-        {
-            const int tpb = std::max(1, 256 / c.NG), threads = (tpb * c.NG + 63) / 64 * 64;
-            // one exchange buffer (two barriers per step) where two do not leave room for a second workgroup on the CU
-            const size_t lds2 = xt_rev_lds_bytes(c.S, c.G, c.EP, D, K, tpb, threads, 2), lds1 = xt_rev_lds_bytes(c.S, c.G, c.EP, D, K, tpb, threads, 1);
-            const int nbuf = (2 * lds2 > 160 * 1024 && 2 * lds1 <= 160 * 1024) ? 1 : 2;
-            const size_t lds = nbuf == 1 ? lds1 : lds2;
-            const void* kp = n_dir > 0 && xt_rev_supported(c.G, c.NG) ? xt_rev_kernel_ptr(c.G, D, K, nbuf) : nullptr;
-            // the merged-state logs (one region per track slot of every block) must fit the budget with at least one block per two CUs:
-            // very long tracks go to the forward-mode kernels instead
-            int Lmax0 = 2;
-            for (auto& d : descs) Lmax0 = std::max(Lmax0, (int)d.L);
-            const size_t slot_doubles = (size_t)tpb * std::max(Lmax0 - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
-            const size_t max_blocks = (ctx->rev_log_mb << 20) / (slot_doubles * sizeof(double));
-            const bool use_rev = !gaps && !d_scores && kp && lds <= 160 * 1024 && max_blocks >= std::max((size_t)ctx->n_cu / 2, descs.size()) &&
-                                 (ctx->grad_rev == 2 || (ctx->grad_rev == 1 && ctx->grad_reg2 == 1 && !r2));
-            if (use_rev) {
-                if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                auto key = std::make_pair(kp, std::make_pair(threads, lds));
-                auto it = ctx->occ_cache.find(key);
-                if (it == ctx->occ_cache.end()) {
-                    int o = 0;
-                    XT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds));
-                    it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
-                }
-                const int occ = it->second;
-                XtKernelArgs a;
-                memset(&a, 0, sizeof(a));
-                xt_fill_args_from_config(c, a);
-                XtRevArgs ra;
-                memset(&ra, 0, sizeof(ra));
-                const double target = std::min((double)occ * ctx->n_cu * ctx->rev_oversub, (double)max_blocks);
-                int Lmax = 2;
-                for (size_t i = 0; i < descs.size(); ++i) Lmax = std::max(Lmax, (int)descs[i].L);
-                // at most max_blocks log regions: the budget holds for the launched grid, not only for the target
-                const int64_t sg = xt_split_descs(target, (int64_t)std::min<size_t>(max_blocks, INT64_MAX), descs, tpb, a.blk_end);
-                if (sg < 0) return xt_fail(ctx, EXTRACK_E_INVALID, "reverse-mode gradient: no grid split within the log budget");
-                const int grid = (int)sg;
-                ra.TB = TB;
-                ra.log_stride = (int64_t)std::max(Lmax - 2, 1) * xt_rev_step_doubles(c.NG, D, K);
-                if ((rc = xt_grad_reserve(ctx, &ctx->d_revlog, &ctx->revlog_cap, (size_t)grid * tpb * (size_t)ra.log_stride))) return rc;
-                if ((rc = xt_grad_reserve(ctx, &ctx->d_revadj, &ctx->revadj_cap, (size_t)TB))) return rc;
-                if ((rc = xt_grad_reserve(ctx, &ctx->d_gpartials, &ctx->gpartials_cap, poff + (size_t)grid * (TB + 1)))) return rc;
-                a.desc = ctx->d_desc + doff;
-                a.ndesc = (int32_t)descs.size();
-                a.blob = ctx->d_blob;
-                a.TPB = tpb;
-                a.min_len = m->min_len;
-                a.locerr_mode = m->locerr_mode;
-                a.KS = b0.KS ? b0.KS : 1;
-                ra.gpartials = ctx->d_gpartials + poff;
-                ra.log = ctx->d_revlog;
-                void* kargs[2] = {(void*)&a, (void*)&ra};
-                XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
-                hipLaunchKernelGGL(xt_grad_reduce, dim3(TB + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, grid, TB + 1, d_out, ctx->d_revadj,
-                                   xt_grad_dst_identity(0));
-                XT_HIP(ctx, hipGetLastError());
-                xt_rev_project(ctx->stream, ctx->d_revadj, ctx->d_dblob, TB, n_dir, d_out + 1);
-                XT_HIP(ctx, hipGetLastError());
-                poff += (size_t)grid * (TB + 1);
-                ctx->launch_info[0] = grid;
-                ctx->launch_info[1] = threads;
-                ctx->launch_info[2] = (int32_t)lds;
-                ctx->launch_info[3] = tpb;
-                ctx->launch_info[4] = occ;
-                ctx->launch_info[5] = ctx->n_cu;
-                doff += g.size();
-                group_done();
-                continue;
-            }
-        }
-        if (r2) {
-            const int tpw = 64 >> (c.F - 1), tpb = tpw * XT_F2_WAVES, threads = 64 * XT_F2_WAVES;
-            // "uniform" directions (xt_r2_uniform_direction, e.g. pBL) cost no per-step work: they ride along with the first pass
-            std::vector<int> full, uni;
-            for (int i = 0; i < n_dir; ++i)
-                ((int)uni.size() < XT_R2_MAXU && xt_r2_uniform_direction(ctx->h_dblob + (size_t)i * TB) ? uni : full).push_back(i);
-            if (full.empty()) {
-                full.push_back(uni.back());
-                uni.pop_back();
-            }
-            // device copy of the tangent blocks in launch order: full directions first, then the uniform ones
-            const int NF = (int)full.size(), NUn = (int)uni.size();
-            if ((rc = xt_grad_reserve(ctx, &ctx->d_dblob2, &ctx->dblob2_cap, (size_t)n_dir * TB))) return rc;
-            for (int i = 0; i < n_dir; ++i) {
-                const int src = i < NF ? full[i] : uni[i - NF];
-                XT_HIP(ctx, hipMemcpyAsync(ctx->d_dblob2 + (size_t)i * TB, ctx->d_dblob + (size_t)src * TB, (size_t)TB * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            static const int r2_maxnp = [] {
-                const char* e = getenv("EXTRACK_R2_MAXNP");
-                const int v = e ? atoi(e) : 8;
-                return v >= 1 && v <= 8 ? v : 8;
-            }();
-            const int npass = (NF + r2_maxnp - 1) / r2_maxnp, per = (NF + npass - 1) / npass;
-            if (d_scores)
-                for (int i = 0; i < n_dir; ++i) cols->idx[i] = i < NF ? full[i] : uni[i - NF];
-            double lo = INFINITY, hi = -INFINITY;
-            for (int k = 0; k < m->locerr_dims && k < 3; ++k) {
-                lo = std::min(lo, m->locerr[k] * m->locerr[k]);
-                hi = std::max(hi, m->locerr[k] * m->locerr[k]);
-            }
-            for (int p0 = 0; p0 < NF; p0 += per) {
-                const int NP = std::min(per, NF - p0);
-                const int NU = p0 == 0 ? NUn : 0, NPT = NP + NU;
-                const void* kp = xt_r2_kernel(c.F, D, K, NP);
-                if (!kp) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
-                XtKernelArgs a;
-                memset(&a, 0, sizeof(a));
-                xt_fill_args_from_config(c, a);
-                XtGradArgs ga;
-                memset(&ga, 0, sizeof(ga));
-                const size_t lds = (size_t)xt_r2_block_bytes(NPT, D, 0, tpw);
-                auto key = std::make_pair(kp, std::make_pair(threads, lds));
-                auto it = ctx->occ_cache.find(key);
-                if (it == ctx->occ_cache.end()) {
-                    int o = 0;
-                    XT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds));
-                    it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
-                }
-                const int occ = it->second;
-                const double target = (double)occ * ctx->n_cu * ctx->oversub;
-                // at most as many blocks as the free part of the partial-sum buffer has rows
-                const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NPT + 1)), descs, tpb, a.blk_end);
-                if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-                const int grid = (int)sg;
-                if (poff + (size_t)grid * (NPT + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-                a.desc = ctx->d_desc + doff;
-                a.ndesc = (int32_t)descs.size();
-                a.blob = ctx->d_blob;
-                a.TPB = tpb;
-                a.min_len = m->min_len;
-                a.locerr_mode = 0;
-                a.KS = 1;
-                a.well_scaled = xt_model_well_scaled(blob, lo, hi) ? 1 : 0;
-                ga.dblob = ctx->d_dblob2 + (size_t)p0 * TB;
-                ga.gpartials = ctx->d_gpartials + poff;
-                ga.NP = NP;
-                ga.TB = TB;
-                ga.NU = NU;
-                ga.udblob = ctx->d_dblob2 + (size_t)NF * TB;
-                ga.score_ld = n_dir;
-                ga.score_col0 = p0;
-                ga.score_ucol0 = NF;
-                void* kargs[2] = {(void*)&a, (void*)&ga};
-                XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
-                XtGradDst dst = xt_grad_dst_identity(0);  // column 1 + i of this launch -> the caller's direction index
-                for (int i = 0; i < NP; ++i) dst.idx[i] = full[p0 + i];
-                for (int i = 0; i < NU; ++i) dst.idx[NP + i] = uni[i];
-                hipLaunchKernelGGL(xt_grad_reduce, dim3(NPT + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, grid, NPT + 1,
-                                   p0 == 0 ? d_out : nullptr, d_out + 1, dst);
-                XT_HIP(ctx, hipGetLastError());
-                poff += (size_t)grid * (NPT + 1);
-                ctx->launch_info[0] = grid;
-                ctx->launch_info[1] = threads;
-                ctx->launch_info[2] = (int32_t)lds;
-                ctx->launch_info[3] = tpb;
-                ctx->launch_info[4] = occ;
-                ctx->launch_info[5] = ctx->n_cu;
-            }
-            doff += g.size();
-            group_done();
-            continue;
-        }
-        // ---- 2 - 4 members per group, <= 256 groups per track: state and tangents in registers, LDS as the exchange medium (xt_gradr.h)
-        // Measured against the LDS-resident kernel below (r03): C3 (3 states, 13 directions) frame_len 6 601 ms vs 1 960 ms, frame_len 4 63 vs 79 ms;
-        // C2-type data through the general kernels (2 states with per-peak errors; in the launcher's order reg2 -> rev -> gradr -> lds the reverse-mode
-        // kernels above now take those models first) frame_len 6 43.8 vs 52.9 ms, frame_len 4 16.1 vs 16.4 ms.
-        if (ctx->grad_reg2 && n_dir > 0 && c.G >= 2 && c.G <= 4 && c.NG <= 256 &&
-            (gaps ? xt_gradr_gap_kernel_ptr(c.G, D, K, 4) : xt_gradr_kernel_ptr(c.G, D, K, 4)) != nullptr) {
-            const int tpb = std::max(1, 256 / c.NG), threads = (tpb * c.NG + 63) / 64 * 64;
-            int NPC;
-            const int per = xt_gradr_per_pass(ctx, n_dir, &NPC);
-            const void* kp = gaps ? xt_gradr_gap_kernel_ptr(c.G, D, K, NPC) : xt_gradr_kernel_ptr(c.G, D, K, NPC);
-            const size_t lds = xt_gradr_lds_bytes(c.S, c.G, c.E, c.EP, c.NG, c.P, D, K, per, tpb);
-            if (kp && lds <= 160 * 1024) {
-                if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                auto key = std::make_pair(kp, std::make_pair(threads, lds));
-                auto it = ctx->occ_cache.find(key);
-                if (it == ctx->occ_cache.end()) {
-                    int o = 0;
-                    XT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds));
-                    it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
-                }
-                const int occ = it->second;
-                for (int p0 = 0; p0 < n_dir; p0 += per) {
-                    const int NP = std::min(per, n_dir - p0);
-                    XtKernelArgs a;
-                    memset(&a, 0, sizeof(a));
-                    xt_fill_args_from_config(c, a);
-                    XtGradArgs ga;
-                    memset(&ga, 0, sizeof(ga));
-                    const double target = (double)occ * ctx->n_cu * 4;
-                    // at most as many blocks as the free part of the partial-sum buffer has rows
-                    const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NP + 1)), descs, tpb, a.blk_end);
-                    if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-                    const int grid = (int)sg;
-                    if (poff + (size_t)grid * (NP + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-                    a.desc = ctx->d_desc + doff;
-                    a.ndesc = (int32_t)descs.size();
-                    a.blob = ctx->d_blob;
-                    a.base_tab = ctx->d_base_tab;
-                    a.off_tab = ctx->d_off_tab;
-                    a.TPB = tpb;
-                    a.min_len = m->min_len;
-                    a.locerr_mode = m->locerr_mode;
-                    a.KS = b0.KS ? b0.KS : 1;
-                    ga.dblob = ctx->d_dblob + (size_t)p0 * TB;
-                    ga.gpartials = ctx->d_gpartials + poff;
-                    ga.NP = NP;
-                    ga.TB = TB;
-                    ga.score_ld = n_dir;
-                    ga.score_col0 = p0;
-                    void* kargs[2] = {(void*)&a, (void*)&ga};
-                    XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
-                    hipLaunchKernelGGL(xt_grad_reduce, dim3(NP + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, grid, NP + 1,
-                                       p0 == 0 ? d_out : nullptr, d_out + 1, xt_grad_dst_identity(p0));
-                    XT_HIP(ctx, hipGetLastError());
-                    poff += (size_t)grid * (NP + 1);
-                    ctx->launch_info[0] = grid;
-                    ctx->launch_info[1] = threads;
-                    ctx->launch_info[2] = (int32_t)lds;
-                    ctx->launch_info[3] = tpb;
-                    ctx->launch_info[4] = occ;
-                    ctx->launch_info[5] = ctx->n_cu;
-                }
-                doff += g.size();
-                group_done();
-                continue;
-            }
-        }
-        // ---- everything else: the LDS-resident kernel (xt_grad.h)
-        if (xt_grad_lds_bytes(c, D, K, std::min(npass_dir, std::max(n_dir, 0)), 1, false) > 160 * 1024)
-            return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "sequence state with one tangent direction does not fit the 160 KiB LDS of a CU");
-        for (int p0 = 0; p0 < std::max(n_dir, 1); p0 += npass_dir) {
-            const int NP = n_dir == 0 ? 0 : std::min(npass_dir, n_dir - p0);
-            GradLauncher l;
-            l.ctx = ctx;
-            memset(&l.a, 0, sizeof(l.a));
-            xt_fill_args_from_config(c, l.a);
-            const XtGradLdsGeom gm = xt_grad_lds_geometry(c, D, K, NP);
-            const bool tan_lds = gm.tan_lds;
-            const int PJ = gm.PJ, tpb = gm.tpb, threads = gm.threads;
-            if (threads > 1024) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "n_states^(frame_len-nb_substeps) > 1024 groups per track is not built");
-            l.threads = threads;
-            l.lds = gm.lds;
-            if (l.lds > 160 * 1024) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "sequence state does not fit the 160 KiB LDS of a CU");
-            // grid: blocks per bucket in proportion to its work, CUs oversubscribed (as the likelihood launcher does)
-            const int occ = std::max(1, std::min((int)((160 * 1024) / l.lds), 2048 / threads));
-            const double target = (double)occ * ctx->n_cu * 4;
-            // at most as many blocks as the free part of the partial-sum buffer has rows
-            const int64_t sg = xt_split_descs(target, (int64_t)((ctx->gpartials_cap - poff) / (NP + 1)), descs, tpb, l.a.blk_end);
-            if (sg < 0) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-            l.grid = (int)sg;
-            if (poff + (size_t)l.grid * (NP + 1) > ctx->gpartials_cap) return xt_fail(ctx, EXTRACK_E_HIP, "gradient partial-sum buffer too small");
-            l.a.desc = ctx->d_desc + doff;
-            l.a.ndesc = (int32_t)descs.size();
-            l.a.blob = ctx->d_blob;
-            l.a.base_tab = ctx->d_base_tab;
-            l.a.off_tab = ctx->d_off_tab;
-            l.a.TPB = tpb;
-            l.a.min_len = m->min_len;
-            l.a.locerr_mode = m->locerr_mode;
-            l.a.KS = b0.KS ? b0.KS : 1;
-            l.ga.dblob = ctx->d_dblob + (size_t)p0 * TB;
-            l.ga.gpartials = ctx->d_gpartials + poff;
-            l.ga.NP = NP;
-            l.ga.TB = TB;
-            l.ga.tan_lds = tan_lds ? 1 : 0;
-            l.ga.PJ = PJ;
-            l.ga.score_ld = n_dir;
-            l.ga.score_col0 = p0;
-            if (!(gaps ? l.run_gaps(c.G, D, K) : xt_grad_dispatch(c.G, D, K, l))) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
-            if (l.herr != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("gradient kernel launch: ") + hipGetErrorString(l.herr));
-            if (NP > 16) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "more than 16 directions per pass");
-            hipLaunchKernelGGL(xt_grad_reduce, dim3(NP + 1), dim3(256), 0, ctx->stream, ctx->d_gpartials + poff, l.grid, NP + 1,
-                               p0 == 0 ? d_out : nullptr, d_out + 1, xt_grad_dst_identity(p0));
-            XT_HIP(ctx, hipGetLastError());
-            poff += (size_t)l.grid * (NP + 1);
-            ctx->launch_info[0] = l.grid;
-            ctx->launch_info[1] = threads;
-            ctx->launch_info[2] = (int32_t)l.lds;
-            ctx->launch_info[3] = tpb;
-            ctx->launch_info[4] = occ;
-            ctx->launch_info[5] = ctx->n_cu;
-        }
-        doff += g.size();
-        group_done();
+    for (const std::vector<XtBucket*>& g : groups) {
+        if ((rc = xt_grad_group_begin(ev, g))) return rc;
+        const XtGradPick pk = xt_grad_pick(ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, g[0]->L, (int)g.size(), ctx->n_cu, gaps, d_scores != nullptr,
+                                           ctx->grad_knobs);
+        if (pk.path == XT_GRAD_NONE) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, xt_grad_refusal_text(pk.refusal));
+        rc = pk.path == XT_GRAD_REV ? xt_grad_rev_launch(ev, pk) : (pk.path == XT_GRAD_REG2 ? xt_grad_run_reg2(ev, pk) : xt_grad_run_passes(ev, pk));
+        if (rc) return rc;
+        xt_grad_group_done(ev, g.size());
     }
     if (d_scores && d_opg) {
-        int rc2 = xt_grad_reserve(ctx, &ctx->d_opgpart, &ctx->opgpart_cap, (size_t)xt_opg_tiles(n_total) * xt_opg_pairs(n_dir));
-        if (rc2) return rc2;
+        if ((rc = xt_grad_reserve(ctx, &ctx->d_opgpart, &ctx->opgpart_cap, (size_t)xt_opg_tiles(n_total) * xt_opg_pairs(n_dir)))) return rc;
         xt_opg_launch(ctx->stream, d_scores, n_total, n_dir, ctx->d_opgpart, d_opg, *cols);
     }
     XT_HIP(ctx, hipGetLastError());

@@ -36,6 +36,7 @@ static const void* gradr_gap_dk(int D, int K)
 }
 
 // Kernel address for (members per group = n_states at nb_substeps 1, dims, loc.-error dims, directions per pass: 3 or 4); nullptr: not built.
+// Built where xt_gradr_built (xt_grad_geom.h) holds.
 const void* xt_gradr_gap_kernel_ptr(int G, int D, int K, int NPC)
 {
     if (NPC == 4) {
@@ -63,7 +64,7 @@ static const void* grad_gap_dk(int D, int K, bool wide)
     return nullptr;
 }
 
-// The LDS-resident body (up to 1024 groups per track); wide: more than 256 threads per workgroup.
+// The LDS-resident body (up to 1024 groups per track); wide: more than 256 threads per workgroup.  Built where xt_grad_lds_built(gaps = true) holds.
 const void* xt_grad_gap_kernel_ptr(int G, int D, int K, bool wide)
 {
     if (G == 2) return grad_gap_dk<2>(D, K, wide);

@@ -22,7 +22,7 @@ static const void* gradr_dk(int D, int K)
     return nullptr;
 }
 
-// Kernel address for (members per group, dims, loc.-error dims, directions per pass: 3 or 4); nullptr: not built.
+// Kernel address for (members per group, dims, loc.-error dims, directions per pass: 3 or 4); nullptr: not built.  Built where xt_gradr_built (xt_grad_geom.h) holds.
 const void* xt_gradr_kernel_ptr(int G, int D, int K, int NPC)
 {
     if (NPC == 4) {

@@ -133,11 +133,23 @@ extern "C" int extrack_create(int device_id, extrack_ctx** out)
         }
     }
     if (const char* ev = getenv("EXTRACK_LL_PATH")) c->ll_reg2 = strcmp(ev, "reg2") == 0 ? 1 : (strcmp(ev, "lds") == 0 ? 0 : c->ll_reg2);
-    if (const char* ev = getenv("EXTRACK_GRAD_PATH")) c->grad_reg2 = strcmp(ev, "lds") == 0 ? 0 : (strcmp(ev, "gradr") == 0 ? 2 : 1);
-    if (const char* ev = getenv("EXTRACK_GRAD_PATH")) c->grad_rev = strcmp(ev, "rev") == 0 ? 2 : (strcmp(ev, "auto") == 0 ? 1 : 0);
-    if (const char* ev = getenv("EXTRACK_REV_OVERSUB")) c->rev_oversub = std::max(1, atoi(ev));
-    if (const char* ev = getenv("EXTRACK_REV_LOG_MB")) c->rev_log_mb = (size_t)std::max(1, atoi(ev));
-    if (const char* ev = getenv("EXTRACK_GRADR_NPC")) c->gradr_npc = atoi(ev) == 4 ? 4 : (atoi(ev) == 3 ? 3 : 0);
+    XtGradKnobs& gk = c->grad_knobs;
+    gk.oversub = c->oversub;
+    if (const char* ev = getenv("EXTRACK_GRAD_PATH")) {
+        gk.grad_reg2 = strcmp(ev, "lds") == 0 ? 0 : (strcmp(ev, "gradr") == 0 ? 2 : 1);
+        gk.grad_rev = strcmp(ev, "rev") == 0 ? 2 : (strcmp(ev, "auto") == 0 ? 1 : 0);
+    }
+    if (const char* ev = getenv("EXTRACK_REV_OVERSUB")) gk.rev_oversub = std::max(1, atoi(ev));
+    if (const char* ev = getenv("EXTRACK_REV_LOG_MB")) gk.rev_log_mb = (size_t)std::max(1, atoi(ev));
+    if (const char* ev = getenv("EXTRACK_GRADR_NPC")) gk.gradr_npc = atoi(ev) == 4 ? 4 : (atoi(ev) == 3 ? 3 : 0);
+    if (const char* ev = getenv("EXTRACK_GRAD_PJ")) {
+        const int v = atoi(ev);
+        if (v == 1 || v == 2 || v == 4 || v == 8) gk.lds_pj = v;
+    }
+    if (const char* ev = getenv("EXTRACK_R2_MAXNP")) {
+        const int v = atoi(ev);
+        if (v >= 1 && v <= 8) gk.r2_maxnp = v;
+    }
     if (const char* ev = getenv("EXTRACK_TH_TT")) {
         int v = atoi(ev);
         if (v >= 1 && v <= 256 && (v & (v - 1)) == 0) c->th_knobs.force_tt = v;
@@ -544,19 +556,7 @@ struct DevLauncher {
     // Occupancy and grid split of kernel kp: sets occ, grid and a.blk_end (false + herr on failure).
     bool plan(const void* kp)
     {
-        auto key = std::make_pair(kp, std::make_pair(threads, lds));
-        auto it = ctx->occ_cache.find(key);
-        if (it == ctx->occ_cache.end()) {
-            if (lds > 64 * 1024) {
-                herr = hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (herr != hipSuccess) return false;
-            }
-            int o = 0;
-            herr = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds);
-            if (herr != hipSuccess) return false;
-            it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
-        }
-        occ = it->second;
+        if ((herr = xt_occupancy(ctx, kp, threads, lds, &occ)) != hipSuccess) return false;
         // Split the grid over the buckets in proportion to their work (track batches x positions).  The CUs are
         // oversubscribed: waves of equal work do NOT progress equally (VALU issue is arbitrated by age), so a static
         // one-wave-set-per-CU split ends in an under-occupied tail; with several block generations per CU the hardware
@@ -777,12 +777,7 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     if (!ok)
         return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, preds ? "posteriors are built for n_states <= 6" : "kernel variant not built");
     if (l.herr != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("kernel launch: ") + hipGetErrorString(l.herr));
-    ctx->launch_info[0] = l.grid;
-    ctx->launch_info[1] = threads;
-    ctx->launch_info[2] = (int32_t)l.lds;
-    ctx->launch_info[3] = tpb;
-    ctx->launch_info[4] = l.occ;
-    ctx->launch_info[5] = ctx->n_cu;
+    xt_set_launch_info(ctx, l.grid, threads, l.lds, tpb, l.occ);
     *grid_out = l.grid;
     return EXTRACK_OK;
 }
@@ -823,20 +818,8 @@ static int xt_loglik_enqueue(extrack_ctx* ctx, const extrack_model* m, double* d
     XT_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = xt_prepare(ctx, m))) return rc;
     // launch groups: buckets with the same (dims, sigma dims), longest first, at most XT_MAX_BUCKETS per launch
-    std::vector<XtBucket*> order;
-    for (auto& b : ctx->buckets) order.push_back(&b);
-    std::stable_sort(order.begin(), order.end(), [](const XtBucket* x, const XtBucket* y) {
-        if (x->D != y->D) return x->D < y->D;
-        if (x->KS != y->KS) return x->KS < y->KS;
-        return x->L > y->L;
-    });
-    std::vector<std::vector<XtBucket*>> groups;
-    for (XtBucket* b : order) {
-        if (groups.empty() || groups.back().size() >= XT_MAX_BUCKETS || groups.back()[0]->D != b->D || groups.back()[0]->KS != b->KS)
-            groups.emplace_back();
-        groups.back().push_back(b);
-    }
-    if (order.size() > (size_t)XT_DESC_CAP / 2) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "too many buckets");
+    const std::vector<std::vector<XtBucket*>> groups = xt_launch_groups(ctx, XT_MAX_BUCKETS);
+    if (ctx->buckets.size() > (size_t)XT_DESC_CAP / 2) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "too many buckets");
     if ((rc = xt_reserve_partials(ctx, groups.size() * xt_max_grid(ctx)))) return rc;
     if (per_track)
         for (auto& b : ctx->buckets)

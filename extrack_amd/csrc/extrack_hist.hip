@@ -122,11 +122,6 @@ extern "C" int extrack_segment_len_hist(extrack_ctx* ctx, const extrack_model* m
     XT_HIP(ctx, hipGetLastError());
     XT_HIP(ctx, hipMemcpyAsync(hist, d_out, (size_t)nbins * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->launch_info[0] = grid;
-    ctx->launch_info[1] = threads;
-    ctx->launch_info[2] = (int32_t)lds;
-    ctx->launch_info[3] = 1;
-    ctx->launch_info[4] = per_cu;
-    ctx->launch_info[5] = ctx->n_cu;
+    xt_set_launch_info(ctx, grid, threads, lds, 1, per_cu);
     return EXTRACK_OK;
 }

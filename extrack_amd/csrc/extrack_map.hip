@@ -135,15 +135,8 @@ int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucke
     xt_build_blob(mh, c, blob);
     if ((rc = xt_upload_blob(ctx, blob))) return rc;
 
-    auto key = std::make_pair(kp, std::make_pair(threads, lds));
-    auto it = ctx->occ_cache.find(key);
-    if (it == ctx->occ_cache.end()) {
-        if (lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int occ = 0;
-        XT_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kp, threads, lds));
-        it = ctx->occ_cache.emplace(key, occ < 1 ? 1 : occ).first;
-    }
-    const int occ = it->second;
+    int occ = 0;
+    XT_HIP(ctx, xt_occupancy(ctx, kp, threads, lds, &occ));
     const int64_t nbatch = (b.N + tpb - 1) / tpb;
     // the launcher's rule for the likelihood (DevLauncher::plan): several block generations per CU, a block of a small launch still walks
     // >= 4 batches, never fewer blocks than fill the chip once
@@ -194,12 +187,7 @@ int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucke
     XT_HIP(ctx, hipMemcpyAsync(states, ma.states, state_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (score) XT_HIP(ctx, hipMemcpyAsync(score, ma.score, (size_t)b.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     XT_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->launch_info[0] = grid;
-    ctx->launch_info[1] = threads;
-    ctx->launch_info[2] = (int32_t)lds;
-    ctx->launch_info[3] = tpb;
-    ctx->launch_info[4] = occ;
-    ctx->launch_info[5] = ctx->n_cu;
+    xt_set_launch_info(ctx, grid, threads, lds, tpb, occ);
     return EXTRACK_OK;
 }
 

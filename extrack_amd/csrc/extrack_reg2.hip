@@ -5,7 +5,8 @@ const void* xt_r2_kernel_f5(int D, int K, int NP);
 const void* xt_r2_kernel_f6(int D, int K, int NP);
 const void* xt_r2_kernel_f7(int D, int K, int NP);
 
-// Kernel address for (frame_len, dims, loc.-error dims, directions per pass); NP = 0: the likelihood-only kernel.  nullptr: not built.
+// Kernel address for (frame_len, dims, loc.-error dims, directions per pass); NP = 0: the likelihood-only kernel.  nullptr: not built.  The gradient
+// kernels (NP >= 1) are built where xt_r2_built (xt_grad_geom.h) holds.
 const void* xt_r2_kernel(int F, int D, int K, int NP)
 {
     if (F == 4) return xt_r2_kernel_f4(D, K, NP);

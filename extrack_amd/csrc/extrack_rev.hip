@@ -25,7 +25,7 @@ static const void* rev_dk(int D, int K)
     return nullptr;
 }
 
-// Kernel address for (members per group, dims, loc.-error dims, exchange buffers per track: 1 | 2); nullptr: not built.
+// Kernel address for (members per group, dims, loc.-error dims, exchange buffers per track: 1 | 2); nullptr: not built.  Built where xt_rev_built (xt_grad_geom.h) holds.
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf)
 {
     if (nbuf == 2) {

@@ -187,22 +187,7 @@ static int xt_th_begin(extrack_ctx* ctx, const extrack_model* m, double threshol
 
 // Launch groups: the buckets that share (dims, sigma dims).  Longest tracks first inside a group: a chunk's plan is a serial walk over its
 // positions, so the long chunks are the critical path of the plan kernel and must not be the last ones to start.
-static std::vector<std::vector<XtBucket*>> xt_th_groups(extrack_ctx* ctx)
-{
-    std::vector<XtBucket*> order;
-    for (auto& b : ctx->buckets) order.push_back(&b);
-    std::stable_sort(order.begin(), order.end(), [](const XtBucket* x, const XtBucket* y) {
-        if (x->D != y->D) return x->D < y->D;
-        if (x->KS != y->KS) return x->KS < y->KS;
-        return x->L > y->L;
-    });
-    std::vector<std::vector<XtBucket*>> groups;
-    for (XtBucket* b : order) {
-        if (groups.empty() || groups.back()[0]->D != b->D || groups.back()[0]->KS != b->KS) groups.emplace_back();
-        groups.back().push_back(b);
-    }
-    return groups;
-}
+static std::vector<std::vector<XtBucket*>> xt_th_groups(extrack_ctx* ctx) { return xt_launch_groups(ctx, SIZE_MAX); }
 
 // Device-side copy of a small host array (bucket descriptors, chunk prefix): grows on demand.
 static int xt_th_upload_small(extrack_ctx* ctx, void** d_buf, size_t* cap, const void* src, size_t bytes)
@@ -464,12 +449,7 @@ static int xt_th_apply(XtThGroup& g, size_t& poff)
     if (getenv("EXTRACK_TH_DEBUG"))
         fprintf(stderr, "[th] chunks %d  plan: lds_mode %d wsP %d wsE %d stP %d | maxG %d sumE %d plan_cap %d | apply: uni %d single %d TT %d threads %d lds %zu bpc %d grid %d\n",
                 a.nchunks, a.ws_lds, a.wsP, a.wsE, a.stP, g.maxG, g.sumE, a.plan_cap, (int)(ag.TT == 64), ag.single_buf, ag.TT, ag.threads, ag.lds, a.bpc, ag.grid);
-    ctx->launch_info[0] = ag.grid;
-    ctx->launch_info[1] = ag.threads;
-    ctx->launch_info[2] = (int32_t)ag.lds;
-    ctx->launch_info[3] = ag.TT;
-    ctx->launch_info[4] = ag.blocks_per_cu;
-    ctx->launch_info[5] = ctx->n_cu;
+    xt_set_launch_info(ctx, ag.grid, ag.threads, ag.lds, ag.TT, ag.blocks_per_cu);
     return EXTRACK_OK;
 }
 

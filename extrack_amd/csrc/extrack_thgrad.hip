@@ -158,12 +158,7 @@ static int xt_th_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, double t
                 XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(NT), kargs, lds, ctx->stream));
                 XT_HIP(ctx, hipGetLastError());
                 rows += (size_t)grid;
-                ctx->launch_info[0] = grid;
-                ctx->launch_info[1] = NT;
-                ctx->launch_info[2] = (int32_t)lds;
-                ctx->launch_info[3] = TT;
-                ctx->launch_info[4] = blocks_per_cu;
-                ctx->launch_info[5] = ctx->n_cu;
+                xt_set_launch_info(ctx, grid, NT, lds, TT, blocks_per_cu);
                 if (getenv("EXTRACK_TH_DEBUG"))
                     fprintf(stderr, "[thgrad2] chunks %d maxG %d Lmax %d | threads %d TT %d lanes/track %d lds %zu bpc %d grid %d log/block %.2f MB total %.1f MB\n", a.nchunks, maxG, Lmax,
                             NT, TT, LPT, lds, a.bpc, grid, ga.ws_stride * 8.0 / 1048576.0, grid * ga.ws_stride * 8.0 / 1048576.0);
@@ -226,12 +221,7 @@ static int xt_th_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, double t
         XT_HIP(ctx, hipLaunchKernel(kp, dim3(grid), dim3(threads), kargs, lds, ctx->stream));
         XT_HIP(ctx, hipGetLastError());
         rows += nw_total;
-        ctx->launch_info[0] = grid;
-        ctx->launch_info[1] = threads;
-        ctx->launch_info[2] = (int32_t)lds;
-        ctx->launch_info[3] = 64;
-        ctx->launch_info[4] = blocks_per_cu;
-        ctx->launch_info[5] = ctx->n_cu;
+        xt_set_launch_info(ctx, grid, threads, lds, 64, blocks_per_cu);
         if (getenv("EXTRACK_TH_DEBUG"))
             fprintf(stderr, "[thgrad] chunks %d maxG %d Lmax %d | NW %d lds %zu bpc %d grid %d ws/wave %.2f MB total %.1f MB\n", a.nchunks, maxG, Lmax, NW, lds,
                     a.bpc, grid, ga.ws_stride * 8.0 / 1048576.0, nw_total * ga.ws_stride * 8.0 / 1048576.0);

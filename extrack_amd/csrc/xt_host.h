@@ -19,6 +19,7 @@
 #include "xt_kernel.h"
 #include "xt_launch_split.h"
 #include "xt_tables.h"
+#include "xt_grad_geom.h"
 #include "xt_th.h"
 #include "xt_th_geom.h"
 
@@ -250,16 +251,11 @@ struct extrack_ctx {
     int n_cu = 0;
     int oversub = 8;  // block generations per CU (EXTRACK_OVERSUB overrides; tuning knob)
     int ll_reg2 = 1;  // 2-state likelihood: 1 = register-resident kernel (xt_reg2.h), 0 = LDS-resident (xt_fast2.h); EXTRACK_LL_PATH=reg2|lds
-    int grad_reg2 = 1;  // gradient kernels: 1 = register-resident where built (xt_reg2.h for 2 states, else xt_gradr.h), 0 = the LDS-resident xt_grad.h
-                        // only, 2 = xt_gradr.h before xt_reg2.h (tests); EXTRACK_GRAD_PATH = reg2 | lds | gradr
-    int grad_rev = 1;   // reverse-mode kernels (xt_rev.h) for 3 / 4 members per group: 1 = where they win, 0 = never, 2 = wherever built; EXTRACK_GRAD_PATH = rev
-    int rev_oversub = 16;  // block generations per CU of the reverse-mode launch (each block owns a log region: fewer blocks, smaller cache footprint)
-    size_t rev_log_mb = 16384;   // budget of those log regions (EXTRACK_REV_LOG_MB): the launch uses fewer blocks to stay within it
+    XtGradKnobs grad_knobs;  // path choice and geometry of the gradient launches (xt_grad_geom.h: EXTRACK_GRAD_PATH, EXTRACK_GRADR_NPC, EXTRACK_REV_LOG_MB, ...)
     double* d_revlog = nullptr;  // merged-state logs of the reverse-mode kernels
     size_t revlog_cap = 0;       // doubles
     double* d_revadj = nullptr;  // adjoint of the model blob [TB]
     size_t revadj_cap = 0;
-    int gradr_npc = 0;  // directions per pass of the xt_gradr.h kernels (0: chosen by the launcher; EXTRACK_GRADR_NPC = 3 | 4 also forces these kernels for small models)
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     std::vector<XtBucket> buckets;
@@ -403,6 +399,45 @@ inline int64_t xt_split_descs(double target, int64_t cap, const std::vector<XtBu
         L[i] = descs[i].L;
     }
     return xt_split_blocks(target, cap, (int)descs.size(), N.data(), L.data(), tracks_per_block, blk_end);
+}
+// Resident workgroups per CU of kernel kp at (threads, lds): the device query, cached per context, at least 1.  On a miss the kernel's
+// dynamic-LDS limit is raised first where lds needs it.
+inline hipError_t xt_occupancy(extrack_ctx* ctx, const void* kp, int threads, size_t lds, int* occ)
+{
+    const auto key = std::make_pair(kp, std::make_pair(threads, lds));
+    auto it = ctx->occ_cache.find(key);
+    if (it == ctx->occ_cache.end()) {
+        hipError_t e = lds > 64 * 1024 ? hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+        int o = 0;
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, kp, threads, lds);
+        if (e != hipSuccess) return e;
+        it = ctx->occ_cache.emplace(key, o < 1 ? 1 : o).first;
+    }
+    *occ = it->second;
+    return hipSuccess;
+}
+// what extrack_last_launch_info reports: the geometry of the last kernel launch
+inline void xt_set_launch_info(extrack_ctx* ctx, int grid, int threads, size_t lds, int tracks_per_block, int occ)
+{
+    const int32_t v[6] = {grid, threads, (int32_t)lds, tracks_per_block, occ, ctx->n_cu};
+    memcpy(ctx->launch_info, v, sizeof(v));
+}
+// Launch groups: the buckets that share (dims, sigma dims), longest tracks first inside a group, at most max_per_group buckets each.
+inline std::vector<std::vector<XtBucket*>> xt_launch_groups(extrack_ctx* ctx, size_t max_per_group)
+{
+    std::vector<XtBucket*> order;
+    for (auto& b : ctx->buckets) order.push_back(&b);
+    std::stable_sort(order.begin(), order.end(), [](const XtBucket* x, const XtBucket* y) {
+        if (x->D != y->D) return x->D < y->D;
+        if (x->KS != y->KS) return x->KS < y->KS;
+        return x->L > y->L;
+    });
+    std::vector<std::vector<XtBucket*>> groups;
+    for (XtBucket* b : order) {
+        if (groups.empty() || groups.back().size() >= max_per_group || groups.back()[0]->D != b->D || groups.back()[0]->KS != b->KS) groups.emplace_back();
+        groups.back().push_back(b);
+    }
+    return groups;
 }
 __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, double* __restrict__ out);
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built

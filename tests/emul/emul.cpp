@@ -28,6 +28,7 @@
 #include "../../extrack_amd/csrc/xt_big.h"
 #include "../../extrack_amd/csrc/xt_launch_split.h"
 #include "../../extrack_amd/csrc/xt_th_geom.h"
+#include "../../extrack_amd/csrc/xt_grad_geom.h"
 
 struct EmulLauncher {
     XtKernelArgs a;
@@ -366,6 +367,24 @@ extern "C" void xt_emul_th_apply_geom(const long long* in, const int* kn, long l
                                              (int)in[10], in[11] != 0, (int)in[12], xt_emul_knobs(kn));
     const long long o[11] = {g.plan_cap, g.TT, g.logTT, g.single_buf, g.mode, g.threads, (long long)g.lds, g.blocks_per_cu, g.bpc, g.grid, g.fits};
     for (int i = 0; i < 11; ++i) out[i] = o[i];
+}
+
+// xt_grad_pick (csrc/xt_grad_geom.h).  in [11]: S, NS, F, D, K, locerr_mode, n_dir, Lmax, nbuckets, gaps, scores; n_cu; kn [8]: the XtGradKnobs fields
+// in declaration order; out [24]: the XtGradPick fields in declaration order (the two pass geometries flattened).  Returns -1 for a model
+// xt_build_config refuses.
+extern "C" int xt_emul_grad_pick(const long long* in, int n_cu, const long long* kn, long long* out)
+{
+    static XtConfig c;  // the digit tables of a long window take longer to build than the decision: kept between calls
+    if ((c.S != in[0] || c.NS != in[1] || c.F != in[2]) && !xt_build_config((int)in[0], (int)in[1], (int)in[2], c).empty()) return -1;
+    XtGradKnobs k;
+    k.grad_reg2 = (int)kn[0], k.grad_rev = (int)kn[1], k.gradr_npc = (int)kn[2], k.rev_log_mb = (size_t)kn[3], k.oversub = (int)kn[4], k.rev_oversub = (int)kn[5];
+    k.lds_pj = (int)kn[6], k.r2_maxnp = (int)kn[7];
+    const XtGradPick p = xt_grad_pick(c, (int)in[3], (int)in[4], (int)in[5], (int)in[6], (int)in[7], (int)in[8], n_cu, in[9] != 0, in[10] != 0, k);
+    const long long o[24] = {p.path, p.refusal, p.tpb, p.threads, (long long)p.lds, p.nbuf, (long long)p.max_blocks, p.log_stride, p.tpw, p.maxnp, p.NPC, p.per, p.npass_dir, p.rem,
+                             p.gm[0].tan_lds, p.gm[0].PJ, p.gm[0].tpb, p.gm[0].threads, (long long)p.gm[0].lds,
+                             p.gm[1].tan_lds, p.gm[1].PJ, p.gm[1].tpb, p.gm[1].threads, (long long)p.gm[1].lds};
+    for (int i = 0; i < 24; ++i) out[i] = o[i];
+    return 0;
 }
 
 // Several length buckets served by ONE emulated launch of the global-state body (csrc/xt_big.h), the way xt_launch_group launches it: grid

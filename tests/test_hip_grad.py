@@ -288,3 +288,43 @@ def test_gradient_more_track_lengths_than_one_launch_serves(S):
         ts.close()
     vs, gs = parts[0][0] + parts[1][0], parts[0][1] + parts[1][1]
     assert abs(vs - v) < 1e-11 * abs(v) and np.allclose(gs, g, rtol=1e-9, atol=1e-9 * np.abs(g).max()), (vs, v, np.abs(gs - g).max())
+
+
+@pytest.mark.parametrize("S,F,env,gaps,knob", [
+    (2, 4, dict(EXTRACK_GRAD_PATH="reg2"), False, 7), (2, 4, dict(EXTRACK_GRAD_PATH="gradr", EXTRACK_GRADR_NPC="4"), False, 23),
+    (2, 4, dict(EXTRACK_GRAD_PATH="lds"), False, 13), (3, 4, dict(EXTRACK_GRAD_PATH="rev"), False, 25), (2, 4, {}, True, 1), (2, 10, {}, True, 1)])
+def test_launcher_follows_the_pick_function(S, F, env, gaps, knob, monkeypatch):
+    """The launcher (csrc/extrack_grad.hip) runs what xt_grad_pick (csrc/xt_grad_geom.h) decides: every kernel family forced in a fresh context,
+    two buckets of 40 tracks (6 and 9 positions, D = 2), three directions - workgroup, LDS bytes and tracks per block of the last launch are
+    those of the matching row of tests/golden/grad_geom_parent.json (the recorded decision of the launcher before the function existed;
+    tests/test_grad_geom_cpu.py).  The LDS bytes of an xt_reg2.h pass depend on which directions are uniform, so the pick leaves them open."""
+    from extrack_amd import _lib, engine, synth
+    from gap_reference import CELL, DT, MODELS, PBL
+    for k in ("EXTRACK_GRAD_PATH", "EXTRACK_GRADR_NPC"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    d = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "grad_geom_parent.json")))
+    row = [r for r in d["rows"] if r[:12] == [S, 1, F, 2, 1, 0, 3, 9, 2, int(gaps), 0, knob]]
+    assert len(row) >= 1 and d["knobs"][knob][:3] == [dict(reg2=1, gradr=2, lds=0, rev=1).get(env.get("EXTRACK_GRAD_PATH"), 1),
+                                                      dict(rev=2).get(env.get("EXTRACK_GRAD_PATH"), 0 if env else 1), int(env.get("EXTRACK_GRADR_NPC", 0))]
+    want = dict(zip(d["out"], row[0][12:]))
+    assert want["path"] == (4 if F == 10 else 3 if gaps else dict(reg2=2, gradr=3, lds=4, rev=1)[env["EXTRACK_GRAD_PATH"]])
+    Ds, Tm, Fs = MODELS[S]
+    ds = np.sqrt(2 * Ds * DT)
+    model = _lib.ModelHandle(ds, Fs, Tm, engine.p_stay_table(ds, S, 1, CELL), PBL, 1, F, 3, 9, locerr=[0.02])
+    ctx = _lib.Context(0)
+    try:
+        for L in (6, 9):
+            tr = synth.brownian_tracks(40, L, list(Ds), Tm, list(Fs), seed=L)
+            ctx.upload_bucket(synth.drop_positions(tr, 0.25, seed=L) if gaps else tr, None)
+        tang = [dict(ds2=np.eye(S)[S - 1]), dict(locerr=[1.0]), dict(TrMat=np.eye(S))]
+        ll, g = ctx.loglik_grad(model, tang, gaps=gaps)
+        info = ctx.last_launch_info()
+    finally:
+        ctx.close()
+    assert np.isfinite(ll) and np.all(np.isfinite(g))
+    threads, lds, tpb = {1: ("threads", "lds", "tpb"), 2: ("threads", None, "tpb"), 3: ("threads", "lds", "tpb"), 4: ("threads0", "lds0", "tpb0")}[want["path"]]
+    assert info["threads"] == want[threads] and info["tracks_per_block"] == want[tpb], (info, want)
+    if lds:
+        assert info["lds_bytes"] == want[lds], (info, want)
