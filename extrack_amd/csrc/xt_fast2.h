@@ -124,6 +124,28 @@ XT_HD void xt_exp_tab_x1(double x, double& p, int& j, int& e)
     p = xt_fma(q, r, 1.0);
     xt_f2_exp_bits(t, j, e);
 }
+// exp(x2 / 2), x2 <= 0: the same evaluation for an argument carried in DOUBLED units (the log-carried g-form step of xt_reg2.h keeps
+// lambda = -2 log weight, so that its -1/2 |c - m|^2 / den needs no multiply by 1/2).  The 1/2 sits in the constants: the scale is halved,
+// the reduction r2 = x2 - k (2 ln2 / 1024) = 2 r uses the doubled constants (doubling is exact: the same k, and r2 is exactly twice the r of
+// xt_exp_tab_x1 up to the same two roundings), and the cubic is written in r2: 1 + r2 (1/2 + r2 (c2 / 4 + r2 / 48)).  Same instruction count
+// as xt_exp_tab_x1, same relative error; the clamp is twice XT_F2_XCLAMP (the same n).
+XT_HD void xt_exp_tab_half_x1(double x2, double& p, int& j, int& e)
+{
+    x2 = x2 > 2.0 * XT_F2_XCLAMP ? x2 : 2.0 * XT_F2_XCLAMP;
+    const double t = xt_fma(x2, 0.5 * XT_F2_EXP_SCALE, XT_MAGIC);
+    const double k = t - XT_MAGIC;
+    double r = xt_fma(k, 2.0 * XT_F2_EXP_HI, x2);
+    r = xt_fma(k, 2.0 * XT_F2_EXP_LO, r);
+#if defined(__HIP_DEVICE_COMPILE__)
+    double q;  // one three-operand instruction, as in xt_exp_tab_x1
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(q) : "s"(1.66666666666666666667e-01 / 8.0), "v"(r), "v"(0.25 * XT_F2_EXP_C2));
+#else
+    double q = xt_fma(1.66666666666666666667e-01 / 8.0, r, 0.25 * XT_F2_EXP_C2);
+#endif
+    q = xt_fma(q, r, 0.5);
+    p = xt_fma(q, r, 1.0);
+    xt_f2_exp_bits(t, j, e);
+}
 // TB[i] = 2^(i / 1024) = T64[i >> 4] * exp((i & 15) ln2 / 1024) at byte offset `off` of the workgroup's LDS; T64: the blob's table (already
 // staged).  The second factor: Taylor to s^7 (s <= 0.0102: truncation far below 1e-18).  Call between two workgroup barriers.
 template <class Ctx>

@@ -64,7 +64,7 @@ XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw)
 }
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
 // Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
-// ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2) (kept in the map; the ratio form of the step no longer reads it), 2 l2} and lnT'[v][prev][q] = ln TAB[v][prev][q] - D/2 ln l2, v = 0 (T), 1 (T * stay)
+// ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2) (kept in the map; the ratio form of the step no longer reads it), 2 l2} and LT2[v][prev][q] = -2 lnT' = -2 (ln TAB[v][prev][q] - D/2 ln l2), v = 0 (T), 1 (T * stay)
 // - at a fixed distance from the entry of table v, so that the step reaches it from the same `tab + [prev][q]` address.
 #define XT_R2_GC_OFF 800
 #define XT_R2_LNT_OFF 960
@@ -318,33 +318,40 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 //     den_q^(-D/2) = (g_q / l2)^(D/2),  -|c - m_bar|^2 / (2 den_q) = A g_q  with  A = -|c - m_bar|^2 / (2 l2)
 //     weight_q = Wm g_q^(D/2) exp(A g_q + lnT'[prev][q]),  lnT' = ln T - D/2 ln l2   (table built per workgroup: no T multiply, no gf)
 // RATIO FORM: none of 1 / W, g_q or c - m_bar is formed.  With Dq_q = Ws d2_q + V = W den_q, the shared reciprocal R = 1 / (Ws Dq0 Dq1)
-// (xt_rcp3) gives h_q = R Dq[1 - q] = 1 / (Ws Dq_q) directly, and everything is written on the un-normalised e_d = c_d Ws - M_d = Ws (c - m_bar)_d:
-//     A g_q = (-1/2 sum_d e_d^2) h_q                              (|c - m_bar|^2 / den_q = (sum e_d^2 / Ws^2) (Ws / Dq_q); no -1 / (2 l2) constant)
+// (xt_rcp3) gives h_q = R Dq[1 - q] = 1 / (Ws Dq_q) directly, and everything is written on the un-normalised e_d = Ws (c - m_bar)_d:
+//     -2 A g_q = (sum_d e_d^2) h_q                                (|c - m_bar|^2 / den_q = (sum e_d^2 / Ws^2) (Ws / Dq_q); no -1 / (2 l2) constant)
 //     k_q = (l2 Ws) h_q = l2 / Dq_q = g_q / Ws   =>   m_q = c - e_d k_q,   v_q = 2 l2 - (l2 Ws) k_q
-//     y_q = Wm (Ws k_q)^(D/2);  D = 2:  y_q = (Wm Ws) k_q         (FIRST: Ws = 1, so h_q = R Dq[1 - q], k_q = l2 h_q, e_d = c_d - m_d)
-// A member's weight is y exp(lx) (s.z = y, a lazily normalised double; lx, a double next to the lane state; s.e is not used): the child's exponential is never
-// taken - lx_q = A g_q + lnT'[prev][q] + base, y_q = Wm g_q^(D/2).  The merge of the NEXT step needs only the ratio of its two members,
-// ONE exponential E = exp(-|lx1 - lx0|) (xt_exp_tab_x1 with its clamp: E = 0 beyond 1.1e7, where the magic-number reduction would leave its
-// range) that scales the member with the smaller lx; base = max(lx0, lx1) is exact.  The absolute magnitude is only needed at the read-out
-// of the last position.  Against the form that exponentiated both children (16 fp64 + 2 table reads for the pair, 6 multiplies, 2 ldexp and
-// the integer exponent bookkeeping) the merge grows by the one exponential and two selects.
-// Lazy re-normalisation (every XT_F2_RENORM-th phase): Wm = frexp_mant(Ws), base += ln2 frexp_exp(Ws).  Range of the lazy mantissa:
+//     y_q = Wm (Ws k_q)^(D/2);  D = 2:  y_q = (Wm Ws) k_q         (FIRST: Ws = 1, so h_q = R Dq[1 - q], k_q = l2 h_q, e_d = (c - m)_d)
+// RESIDUAL FORM: the recursion is translation invariant - it only ever uses a position minus a member's mean.  The members of a g-form launch
+// carry r = c_next - m (in s.m) instead of m, and the staged array holds the position deltas dc_t = c_{t+1} - c_t (xt_r2_body: stage).  The merge
+// E_d = w0 r0_d + w1 r1_d IS e_d (no c_d Ws - M_d), the children are r_q[d] = dc_d + E_d k_q (m_q = c - e k_q, minus it from c_next), the
+// merge-free first step and the read-out take r for c - m, and the warm-up (xt_r2_chain_g) never forms c - m.  No absolute coordinate is
+// read on these paths; a delta is rounded once at ulp(|c|), as c - m was.
+// A member's weight is y exp(-lambda / 2) (s.z = y, a lazily normalised double; lambda, a double next to the lane state; s.e is not used): the
+// child's exponential is never taken, and the log part is carried in DOUBLED, NEGATED units so that -1/2 sum e_d^2 needs no multiply:
+//     lambda_q = (sum_d e_d^2) h_q + LT2[prev][q] + base,   LT2 = -2 lnT'   (the table is built in these units),   y_q = Wm g_q^(D/2).
+// The merge of the NEXT step needs only the ratio of its two members, ONE exponential E = exp(-|lambda1 - lambda0| / 2) (xt_exp_tab_half_x1:
+// the 1/2 is in its constants; clamp at |d lambda| = 2.2e7, E = 0 beyond, where the magic-number reduction would leave its range - the same
+// integer n as xt_exp_tab_x1 at 1.1e7) that scales the member with the LARGER lambda; the other keeps scale 1 and base = min(lambda0, lambda1)
+// is exact.  The absolute magnitude is only needed at the read-out of the last position (x = -1/2 (|r|^2 / den + lambda): one fma).
+// Lazy re-normalisation (every XT_F2_RENORM-th phase): Wm = frexp_mant(Ws), base -= 2 ln2 frexp_exp(Ws).  Range of the lazy mantissa:
 // y = Wm g^(D/2) with g = l2 / den in [1e-16, 1] (well-scaled bounds: l2 >= 1e-12, den <= 1e4) and a merge at most doubles the sum
 // (E <= 1): three un-normalised steps stay within [1e-72, 8]; the products of a step are then Ws Dq0 Dq1 = W^3 den^2 >= 1e-240 (<= 8^3 * 1e8),
 // h_q = 1 / (W^2 den_q) <= 1 / (W_min den_min W_min) = 1e144 * 1e12, k_q = l2 h_q Ws <= 1 / W_min = 1e72 (g_q <= 1), e_d^2 <= 64 |c - m_bar|^2,
 // sum e_d^2 h_q = |c - m_bar|^2 / den_q is the same number as before, and Wm Ws <= 64, >= 1e-144 (Wm = Ws between re-normalisations) - all
-// far inside the fp64 range; the transition weight and l2^(-D/2) live in lx.
-// Re-centring (phase XT_R2_RC_H, once per F - 1 steps): lx is rounded at ulp(|lx|), so it must not grow with the accumulated
-// log-likelihood.  The lanes of a track take the maximum of their truncated bases through an integer atomic max on the track's LDS cell
-// (LDS and cx.wave_sync() only): sh, an integer common to the track.  base -= sh (exact, or one rounding at the ulp of the small
-// difference) and the lane's LDS accumulator += sh (integers: exact); the read-out adds the accumulator to the track's log-likelihood.
-// The reference has to be the LARGEST base, not that of a fixed lane: a fixed lane's sequence may be hopeless (a still state on a moving
-// track is at -600 per step), and shifting by its base leaves |lx| in the thousands on the lanes that matter (measured: 1e-12 on
-// 33-position tracks at l2 = 1e-10).  In a re-normalisation phase y is in [0.5, 1), so the largest base is the dominant group's
-// log-weight to within ln 2, and the lanes that matter end within a few nats of 0; lanes far below are negligible at the read-out.
-// No execution mask and no branch: the step stays one basic block.  Between two re-centrings |lx| grows by at most F - 1 steps' worth
-// of log-weight (a few nats per step on ordinary data; at small l2 the lazy mantissa takes D/2 ln(den / l2) per step out of it until the next
-// re-normalisation: |lx| < 150 at l2 = 1e-12, D = 3, ulp 2.8e-14).
+// far inside the fp64 range; the transition weight and l2^(-D/2) live in lambda.
+// Re-centring (phase XT_R2_RC_H, once per F - 1 steps): lambda is rounded at ulp(|lambda|), so it must not grow with the accumulated
+// log-likelihood.  The lanes of a track take the MINIMUM of their truncated bases (an integer atomic max of the negated integers on the
+// track's LDS cell; LDS and cx.wave_sync() only): sh, an integer common to the track, in lambda units.  base -= sh (exact, or one rounding at
+// the ulp of the small difference) and the lane's LDS accumulator += sh (integers: exact); the read-out adds -1/2 x the accumulator to the
+// track's log-likelihood.  The reference has to be the SMALLEST base (the largest log-weight), not that of a fixed lane: a fixed lane's
+// sequence may be hopeless (a still state on a moving track is at -600 per step), and shifting by its base leaves |lambda| in the thousands on
+// the lanes that matter (measured in log units: 1e-12 on 33-position tracks at l2 = 1e-10).  In a re-normalisation phase y is in [0.5, 1), so the
+// smallest base is -2 x the dominant group's log-weight to within 2 ln 2, and the lanes that matter end within a few units of 0; lanes far
+// above are negligible at the read-out.  No execution mask and no branch: the step stays one basic block.  Between two re-centrings |lambda|
+// grows by at most F - 1 steps' worth of 2 x log-weight (a few units per step on ordinary data; at small l2 the lazy mantissa takes
+// D/2 ln(den / l2) per step out of the log-weight until the next re-normalisation: |lambda| < 300 at l2 = 1e-12, D = 3, ulp 5.7e-14, i.e. 2.8e-14
+// in the log-likelihood, as before the doubling: lambda / 2 has the rounding error of lambda halved).
 #ifndef XT_R2_RC_H
 #define XT_R2_RC_H 0  // re-centring phase: a re-normalisation phase
 #endif
@@ -390,7 +397,7 @@ XT_HD int xt_r2_tid8(Ctx& cx)
 #endif
 }
 template <int F, int D, int H, bool FIRST = false, class Ctx>
-XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2], int& pk, int tab, const double* c)
+XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int& pk, int tab, const double* dc)
 {
     constexpr int NGB = F - 1;
     constexpr int XB = xt_r2_gbit(F, H);
@@ -402,42 +409,45 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
         TD2[q] = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + io[q]);
-        LT[q] = xt_at<double>(lds, tab + XT_R2_LNT_REL + io[q]);
+        LT[q] = xt_at<double>(lds, tab + XT_R2_LNT_REL + io[q]);  // -2 lnT'
     }
     const double l2 = xt_at<double>(lds, 0), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
 
-    // ---- merge (members carry v = l2 + u): the member with the smaller lx is scaled by exp(-|lx1 - lx0|)
-    double w0 = 1.0, w1 = 0.0, base = lx[0];
+    // ---- merge (members carry v = l2 + u and r = c - m): the member with the larger lambda is scaled by exp(-|lambda1 - lambda0| / 2)
+    double w0 = 1.0, w1 = 0.0, base = lam[0];
     if (!FIRST) {
-        const double dl = lx[1] - lx[0];
+        const double dl = lam[1] - lam[0];
         double p;
         int j, n;
-        xt_exp_tab_x1(-fabs(dl), p, j, n);
+        xt_exp_tab_half_x1(-fabs(dl), p, j, n);
         const double E = xt_ldexp(xt_at<double>(lds, XT_F2_EXPB_OFF + j * 8) * p, n);  // n <= 0
-        const bool up = dl > 0.0;
+        const bool up = dl < 0.0;
         w0 = s.z[0] * (up ? E : 1.0);
         w1 = s.z[1] * (up ? 1.0 : E);
-        base = up ? lx[1] : lx[0];
+        base = up ? lam[1] : lam[0];
     }
     const double Ws = FIRST ? 1.0 : w0 + w1;
-    double M[D];
+    double ed[D], esq = 0.0;  // Ws (c - m_bar)
     XT_UNROLL
-    for (int d = 0; d < D; ++d) M[d] = FIRST ? s.m[0][d] : xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
+    for (int d = 0; d < D; ++d) {
+        ed[d] = FIRST ? s.m[0][d] : xt_fma(w1, s.m[1][d], w0 * s.m[0][d]);
+        esq = xt_fma(ed[d], ed[d], esq);
+    }
     const double V = FIRST ? s.u[0][0] : xt_fma(w1, s.u[1][0], w0 * s.u[0][0]);
     constexpr bool RN = !FIRST && (H % XT_F2_RENORM) == 0;
     const double Wm = FIRST ? s.z[0] : (RN ? xt_frexp_mant(Ws) : Ws);
-    if (RN) base = xt_fma((double)xt_frexp_exp(Ws), XT_LN2, base);
+    if (RN) base = xt_fma((double)xt_frexp_exp(Ws), -2.0 * XT_LN2, base);
     if (!FIRST && H == XT_R2_RC_H) {
-        // re-centring: the integer shift is the largest (truncated) base among the track's lanes - an atomic max on the track's LDS cell,
-        // which every lane of the track reset one phase later in the previous pass (or at position 0)
+        // re-centring: the integer shift is the smallest (truncated) base among the track's lanes - an atomic max of the negated integers on the
+        // track's LDS cell, which every lane of the track reset one phase later in the previous pass (or at position 0)
         const int tid8 = xt_r2_tid8(cx);
         const int rc0 = xt_r2_rc0(D, 0, XtR2Geom<F>::TPW);  // g-form launches stage no per-peak errors (KS = 0)
         const int cell = rc0 + (tid8 & ~(xt_r2_gmask(F) * 8));
-        cx.atomic_max_i32(&xt_at<int>(lds, cell), (int)fmin(fmax(base, -1e9), 1e9));  // a NaN base (poisoned track) counts as -1e9
+        cx.atomic_max_i32(&xt_at<int>(lds, cell), (int)fmin(fmax(-base, -1e9), 1e9));  // a NaN base (poisoned track) counts as lambda = +1e9
         cx.wave_sync();
-        const int sh = xt_at<int>(lds, cell);
-        base -= (double)sh;
-        xt_at<unsigned int>(lds, rc0 + XT_R2_RC_ARR + tid8) += (unsigned int)sh;  // read back as int; wraps only on a poisoned track (-1e9 per pass)
+        const int nsh = xt_at<int>(lds, cell);  // - min over the lanes
+        base += (double)nsh;
+        xt_at<unsigned int>(lds, rc0 + XT_R2_RC_ARR + tid8) -= (unsigned int)nsh;  // read back as int; wraps only on a poisoned track (1e9 per pass)
     }
     if (!FIRST && H == (XT_R2_RC_H + 1) % NGB) xt_at<int>(lds, xt_r2_rc0(D, 0, XtR2Geom<F>::TPW) + (xt_r2_tid8(cx) & ~(xt_r2_gmask(F) * 8))) = XT_R2_RC_NONE;
 
@@ -446,37 +456,75 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lx)[2
     const double R = xt_rcp3(Ws * (Dq0 * Dq1));
     const double h[2] = {R * Dq1, R * Dq0};
     const double l2W = FIRST ? l2 : l2 * Ws;
-    double ed[D], esq = 0.0;
-    XT_UNROLL
-    for (int d = 0; d < D; ++d) {
-        ed[d] = FIRST ? c[d] - M[d] : xt_fma(c[d], Ws, -M[d]);  // Ws (c - m_bar)
-        esq = xt_fma(ed[d], ed[d], esq);
-    }
-    const double Ah = -0.5 * esq;
     const double WmW = FIRST ? Wm : Wm * Ws;
-    double ny[2], nl[2], nm[2][D], nv[2];
+    double ny[2], nl[2], nr[2][D], nv[2];
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
         const double k = l2W * h[q];
         ny[q] = D == 2 ? WmW * k : Wm * xt_pow_half<D>(FIRST ? k : Ws * k);
-        nl[q] = xt_fma(Ah, h[q], LT[q]) + base;
+        nl[q] = xt_fma(esq, h[q], LT[q]) + base;
         XT_UNROLL
-        for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(-ed[d], k, c[d]);
+        for (int d = 0; d < D; ++d) nr[q][d] = xt_fma(ed[d], k, dc[d]);
         nv[q] = xt_fma(-l2W, k, l22);
     }
     cx.template pair_exchange<XB>(ny[0], ny[1]);
     cx.template pair_exchange<XB>(nl[0], nl[1]);
     XT_UNROLL
-    for (int d = 0; d < D; ++d) cx.template pair_exchange<XB>(nm[0][d], nm[1][d]);
+    for (int d = 0; d < D; ++d) cx.template pair_exchange<XB>(nr[0][d], nr[1][d]);
     cx.template pair_exchange<XB>(nv[0], nv[1]);
     XT_UNROLL
     for (int q = 0; q < 2; ++q) {
         s.z[q] = ny[q];
-        lx[q] = nl[q];
+        lam[q] = nl[q];
         XT_UNROLL
-        for (int d = 0; d < D; ++d) s.m[q][d] = nm[q][d];
+        for (int d = 0; d < D; ++d) s.m[q][d] = nr[q][d];
         s.u[q][0] = nv[q];
     }
+}
+
+// Warm-up of a g-form launch: the chain of xt_r2_chain in the quantities the g-form step carries - (y, lambda, r = c_next - m, v = l2 + u) -
+// with NO exponential, no frexp per position and no integer exponent.  One position of the lane's own state path, g = l2 / den, den = d2 + v:
+//     y *= g^(D/2),   lambda += |r|^2 / den - 2 lnT'[prev][q],   v = 2 l2 - l2 g,   r_d = dc_d + r_d g      (dc: the staged position deltas)
+// on the tables the steady step reads (the stay factor sets in at stay_from).  Range: g in [1e-16, 1] (well-scaled bounds), at most F - 2 = 5
+// positions: y >= 1e-120 times the initial fraction.  The first full step and the merges after it form W^3-sized products, so the chain hands
+// over a normalised mantissa: ONE frexp at its end, its exponent folded into lambda.  Lanes whose digits are still dummies (a bucket too
+// short to fill the window) end at y = 0 with finite lambda, r, v; such a bucket goes from here straight to the read-out.
+template <int F, int D, class Ctx, class GetPos>
+XT_HD void xt_r2_chain_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int T, int stay_from, GetPos& getpos)
+{
+    constexpr int NGB = F - 1;
+    const int lane = xt_opaque(cx.lane());
+    const double l2 = xt_at<double>(lds, 0), l22 = xt_at<double>(lds, XT_R2_GC_OFF + 8);
+    double y = s.z[0], la = lam[0], v = s.u[0][0];
+    XT_UNROLL
+    for (int t = 1; t < NGB; ++t) {
+        if (t > T) break;  // wave-uniform (per bucket)
+        const int prev = (lane >> xt_r2_gbit(F, t == 1 ? NGB - 1 : t - 2)) & 1;
+        const int q = (lane >> xt_r2_gbit(F, t - 1)) & 1;
+        const int io = (prev * 2 + q) * 8;  // [prev][q] byte offset
+        const double LT = xt_at<double>(lds, XT_R2_LNT_OFF + (t >= stay_from ? 32 : 0) + io);
+        const double d2 = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + io);
+        double dc[D], l2u[1];
+        getpos(t, dc, l2u);
+        const double rd = xt_rcp3(d2 + v);
+        const double g = l2 * rd;
+        double rsq = 0.0;
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) rsq = xt_fma(s.m[0][d], s.m[0][d], rsq);
+        y *= xt_pow_half<D>(g);
+        la = xt_fma(rsq, rd, la + LT);
+        v = xt_fma(-l2, g, l22);
+        XT_UNROLL
+        for (int d = 0; d < D; ++d) s.m[0][d] = xt_fma(s.m[0][d], g, dc[d]);
+    }
+    int dummy = 0;  // lane bits of digits that are still dummies (time < 0)
+    XT_UNROLL
+    for (int i = 0; i < NGB - 1; ++i)
+        if (i >= T) dummy |= 1 << xt_r2_gbit(F, i);
+    const bool live = (lane & dummy) == 0;
+    s.z[0] = live ? xt_frexp_mant(y) : 0.0;
+    lam[0] = xt_fma((double)xt_frexp_exp(y), -2.0 * XT_LN2, la);
+    s.u[0][0] = v;
 }
 
 // all-reduce over the lanes of a track (the F - 1 group bits)
@@ -610,7 +658,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int i = cx.tid();
             const double l2 = smem[0];
             if (i < 8)
-                xt_at<double>(lds, XT_R2_LNT_OFF + i * 8) = log(smem[XT_BLOB_HDR + i]) - 0.5 * D * log(l2);
+                xt_at<double>(lds, XT_R2_LNT_OFF + i * 8) = -2.0 * (log(smem[XT_BLOB_HDR + i]) - 0.5 * D * log(l2));
             else
                 xt_at<double>(lds, XT_R2_GC_OFF + (i - 8) * 8) = i == 8 ? -0.5 / l2 : 2.0 * l2;
         }
@@ -671,8 +719,18 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 const int64_t tkc = tk < b.N ? tk : b.N - 1;
                 const int pp = p0 + r / D;
                 if (pp < L) {
-                    const double v = b.tracks[(tkc * L + p0) * D + r];
-                    pos[i] = v;
+                    const double* const src = b.tracks + (tkc * L + p0) * D + r;
+                    const double v = src[0];
+                    if constexpr (NP == 0 && K == 1) {
+                        // g-form launches stage the position DELTAS c_{t+1} - c_t (0 at the last position): their steps never read an
+                        // absolute coordinate.  The next position is in the cache line just read or the one after (a chunk's last delta
+                        // reaches into the next chunk); both loads are issued before either is used, so the wave waits for memory once.
+                        // The NaN flag is set from the raw position.
+                        const double vn = src[pp + 1 < L ? D : 0];
+                        pos[i] = gform ? vn - v : v;
+                    } else {
+                        pos[i] = v;
+                    }
                     if (v != v) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + t_) * 4) = 1;
                 }
             }
@@ -711,7 +769,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
 
         XtR2Lane<D, K, NP> s;
-        double lx[2] = {0.0, 0.0};  // log part of the members' weights (xt_r2_step_g); the read-out adds it to the exponential's argument: zero unless log-carried steps ran
+        double lam[2] = {0.0, 0.0};  // g-form launches: -2 x the log part of the members' weights (xt_r2_step_g); stays zero otherwise
 #define XT_R2_PHASE(H, ZF_, LAZY_)                                                                     \
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
@@ -724,7 +782,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
         getpos(t, c, l2);                                                                              \
-        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lx, pk, XT_R2_TABSEL, c);                    \
+        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lam, pk, XT_R2_TABSEL, c);                   \
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
@@ -809,6 +867,11 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                     XT_UNROLL
                     for (int k = 0; k < K; ++k) s.u[q][k] = l20[k];
                 }
+                if constexpr (NP == 0 && K == 1) {
+                    // g-form launches: the members carry r = c_next - m (position 0: the staged delta that getpos just read), v = l2 + u and
+                    // weights y exp(-lambda / 2), from here to the read-out of the last position
+                    if (gform) s.u[0][0] = s.u[1][0] = 2.0 * l20[0];
+                }
                 XT_UNROLL
                 for (int pp = 0; pp < NP; ++pp) {
                     const int tb = XT_R2_TAN0 + pp * XT_R2_TB * 8;
@@ -826,17 +889,22 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                     if (chain) {
                         // positions 1 .. F - 2 as per-lane chains, position F - 1 without the merge of the dead member: t = F after that
                         const int T = L - 2 < NGB - 1 ? L - 2 : NGB - 1;
-                        xt_r2_chain<F>(cx, lds, s, T, stay_from, getpos);
+                        bool chain_done = false;
+                        if constexpr (K == 1) {
+                            if (gform) {
+                                xt_r2_chain_g<F>(cx, lds, s, lam, T, stay_from, getpos);
+                                s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lambda
+                                chain_done = true;
+                            }
+                        }
+                        if (!chain_done) xt_r2_chain<F>(cx, lds, s, T, stay_from, getpos);
                         if (L - 2 >= F - 1) {
                             double c[D], l2[K];
                             getpos(F - 1, c, l2);
                             bool first_done = false;
                             if constexpr (K == 1) {
-                                if (gform) {  // from here on the members carry v = l2 + u and weights y exp(lx) (until the read-out of the last position)
-                                    s.u[0][0] += l2[0];
-                                    lx[0] = (double)s.e[0] * XT_LN2;
-                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lx, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
-                                    s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lx now
+                                if (gform) {
+                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lam, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
                                     first_done = true;
                                 }
                             }
@@ -860,7 +928,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             double cl[D], l2l[K];
             getpos(tlast, cl, l2l);
             if constexpr (NP == 0 && K == 1) {
-                if (gform && L - 2 >= F - 1) l2l[0] = 0.0;  // the g-form steps left v = l2 + u in the members
+                if (gform) l2l[0] = 0.0;  // g-form launches: the members carry v = l2 + u, and r = cl - m below
             }
             const int hp = (tlast - 2 + NGB) % NGB;  // group bit of the newest digit
             const int pbit = (F == 7 || hp < 2) ? hp : hp + 1;
@@ -887,6 +955,9 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 XT_UNROLL
                 for (int d = 0; d < D; ++d) {
                     dq[Q][d] = cl[d] - s.m[Q][d];
+                    if constexpr (NP == 0 && K == 1) {
+                        if (gform) dq[Q][d] = s.m[Q][d];
+                    }
                     dsqQ[Q] = xt_fma(dq[Q][d], dq[Q][d], dsqQ[Q]);
                 }
                 double x[2], gf[2];
@@ -901,8 +972,10 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                             r = xt_rcp(d2 + s.u[Q][0] + l2l[0]);
                             rr[Q * 2 + q][0] = r;
                         }
-                        x[q] = -0.5 * dsqQ[Q] * r;
-                        if constexpr (NP == 0) x[q] += lx[Q];  // log-carried weights (xt_r2_step_g): y exp(lx), e = 0
+                        if constexpr (NP == 0)
+                            x[q] = -0.5 * xt_fma(dsqQ[Q], r, lam[Q]);  // log-carried weights (xt_r2_step_g): y exp(-lambda / 2), e = 0; lambda = 0 otherwise
+                        else
+                            x[q] = -0.5 * dsqQ[Q] * r;
                         gf[q] = xt_pow_half<D>(r);
                     } else {
                         double xx = 0.0, gg = 1.0;
@@ -987,7 +1060,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int lz = xt_opaque(cx.lane());
             const int64_t trk = batch * TPW + xt_r2_slot<F>(lz);  // formed again: not held across the step loop
             if (trk < b.N && (lz & GMASK) == 0) {
-                const double rcs = (double)xt_at<int>(lds, rcacc());  // 0 unless log-carried steps ran
+                const double rcs = -0.5 * (double)xt_at<int>(lds, rcacc());  // the re-centring shifts, in lambda units; 0 unless log-carried steps ran
                 if (b.ll_out) b.ll_out[trk] = log(sum) + (double)fe * XT_LN2 + b.ll_const + rcs;
                 xt_at<double>(lds, rcsum()) += rcs;
                 const int ab = accb();

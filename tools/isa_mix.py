@@ -5,10 +5,10 @@ reads the result (profiles/isa_mix.json) for its fp64-issue figures instead of h
     python tools/isa_mix.py            # compiles xt_ll_r2_kernel<6,2,1> into /tmp, writes profiles/isa_mix.json
 
 Method: the likelihood-only register-resident kernel (csrc/xt_reg2.h) unrolls its step loop over the F - 1 exchange phases in three
-variants; the basic blocks with >= 50 fp64 vector instructions and the table reads are the steps.  The steady-state ones (well-scaled model:
+variants; the basic blocks with >= 40 fp64 vector instructions and the table reads are the steps.  The steady-state ones (well-scaled model:
 zero-free, lazily re-normalised) are the 2 (F - 1) with the fewest instructions among the blocks of the innermost loops (the loop depth the
-compiler notes at every block label); the first step-sized block outside them is the merge-free first step (position F - 1; the read-out of the last position follows it), and the F - 2 blocks with one
-v_rcp_f64 right before it are the warm-up chain (positions 1 .. F - 2, one block each).  Counts are per wave-step (one wavefront = 64 / 2^(F-1) tracks,
+compiler notes at every block label); the first step-sized block outside them is the merge-free first step (position F - 1; the read-out of the last position follows it), and the warm-up chain (positions 1 .. F - 2)
+is the one block with F - 2 v_rcp_f64 (the g-form launches' chain, which the headline runs), else the F - 2 blocks with one v_rcp_f64 right before the first step.  Counts are per wave-step (one wavefront = 64 / 2^(F-1) tracks,
 one position)."""
 import json, os, re, subprocess, sys, tempfile
 
@@ -35,7 +35,7 @@ blocks, cur = [], None
 for line in open(os.path.join(tmp, asm)):
     if line.startswith(".LBB") or line.startswith("_Z"):
         dm = re.search(r"Depth=(\d+)", line)
-        cur = dict(name=line.split(":")[0], depth=int(dm.group(1)) if dm else 0, f64=0, fma=0, valu32=0, lds=0, salu=0, vmem=0, trans=0)
+        cur = dict(name=line.split(":")[0], depth=int(dm.group(1)) if dm else 0, f64=0, fma=0, valu32=0, lds=0, salu=0, vmem=0, trans=0, xch=0)
         blocks.append(cur)
         continue
     if cur is not None and line.lstrip().startswith(";") and "Depth=" in line:  # the loop comment may follow the label on a line of its own
@@ -44,6 +44,8 @@ for line in open(os.path.join(tmp, asm)):
     if cur is None or not line.startswith("\t") or line.startswith("\t.") or line.startswith("\t;"):
         continue
     op = line.split()[0]
+    if "permlane" in op or "_dpp" in op or " quad_perm:" in line or " row_" in line:
+        cur["xch"] += 1  # an instruction of the lane exchange
     if op.startswith("v_"):
         if "_f64" in op or op in ("v_lshl_add_u64",):
             cur["f64"] += 1
@@ -59,12 +61,19 @@ for line in open(os.path.join(tmp, asm)):
         cur["salu"] += 1
     elif op.startswith(("global_", "flat_", "buffer_", "scratch_")):
         cur["vmem"] += 1
-steps = sorted([b for b in blocks if b["f64"] >= 50 and b["lds"] >= 4], key=lambda b: b["f64"] + b["valu32"])
+steps = sorted([b for b in blocks if b["f64"] >= 40 and b["lds"] >= 4], key=lambda b: b["f64"] + b["valu32"])
 maxd = max(b["depth"] for b in steps)
 ss = [b for b in steps if b["depth"] == maxd][:2 * (F - 1)]  # the step loop is inlined twice (before / after the stay-in-FOV factor sets in): both copies of the F - 1 phases
-first = sorted([b for b in steps if b["depth"] < maxd], key=blocks.index)[:1]  # the read-out of the last position, a block of this size too, comes after it
+# the merge-free first step: outside the innermost loops, one reciprocal, and - what tells it from the read-out of the last position - a lane
+# exchange.  Both the general and the g-form first step are compiled; the headline runs the g-form one, the smaller of the two (the compiler
+# may split it: its block with the exchange and the reciprocal is what is counted)
+first = sorted([b for b in blocks if b["depth"] < maxd and b["trans"] == 1 and b["xch"] >= 8 and b["f64"] >= 20 and b["lds"] >= 4], key=lambda b: b["f64"])[:1]
 at = blocks.index(first[0]) if len(first) == 1 else 0
-chain = [b for b in blocks[:at] if b["depth"] == maxd - 1 and 20 <= b["f64"] < 50 and b["trans"] == 1][-(F - 2):] if at else []
+chain = [b for b in blocks[:at] if b["depth"] == maxd - 1 and 10 <= b["f64"] < 40 and b["trans"] == 1][-(F - 2):] if at else []
+# the g-form launches' chain (xt_r2_chain_g) has no exponential and compiles to ONE block for the full window: F - 2 reciprocals, no step's table pair
+gchain = [b for b in blocks if b["depth"] == maxd - 1 and b["trans"] == F - 2 and b["f64"] < 40 * (F - 2)]
+if len(gchain) == 1:
+    chain = gchain
 n = float(len(ss))
 mix = {k: sum(b[k] for b in ss) / n for k in ("f64", "fma", "valu32", "lds", "salu", "vmem", "trans")}
 tpw = 64 >> (F - 1)
