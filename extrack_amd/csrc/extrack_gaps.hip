@@ -1,9 +1,9 @@
 // libextrack_hip.so: the gap-aware instantiations of the fixed-window body (xt_kernel.h, GAPS = true) behind extrack_loglik_gaps /
-// extrack_predict_gaps, and their lookup.  The launch sites live in extrack_hip.hip (xt_launch_group), which gives them the geometry of
+// extrack_predict_gaps, and their lookup.  The launch sites live in extrack_ll.hip (xt_launch_group), which gives them the geometry of
 // xt_track_kernel; the definition of a gap is in DESIGN.md section 18.
 #include "xt_host.h"
 
-// Waves per SIMD asked of the register allocator: the values of xt_track_kernel (extrack_hip.hip, measured there).  The gap branch adds a
+// Waves per SIMD asked of the register allocator: the values of xt_track_kernel (extrack_ll.hip, measured there).  The gap branch adds a
 // handful of LDS stores and no live value across the step, so the same bounds are taken over unmeasured.
 #ifndef XT_LL_WAVES
 #define XT_LL_WAVES 4
@@ -41,6 +41,7 @@ static const void* gap_dk(int D, int K, bool preds, bool wide)
 }
 
 // Kernel address for (members per group = n_states at nb_substeps 1, dims, loc.-error dims, posteriors, more than 256 threads per workgroup).
+// Built where xt_ll_gap_built (xt_ll_geom.h) holds.
 const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide)
 {
     if (G == 2) return gap_dk<2>(D, K, preds, wide);

@@ -138,7 +138,7 @@ int xt_map_states_launch(extrack_ctx* ctx, const extrack_model* m, int32_t bucke
     int occ = 0;
     XT_HIP(ctx, xt_occupancy(ctx, kp, threads, lds, &occ));
     const int64_t nbatch = (b.N + tpb - 1) / tpb;
-    // the launcher's rule for the likelihood (DevLauncher::plan): several block generations per CU, a block of a small launch still walks
+    // the launcher's rule for the likelihood (extrack_ll.hip: xt_ll_plan): several block generations per CU, a block of a small launch still walks
     // >= 4 batches, never fewer blocks than fill the chip once
     int64_t target = (int64_t)occ * ctx->n_cu * ctx->oversub;
     if (!ctx->oversub_forced) target = std::max<int64_t>((int64_t)occ * ctx->n_cu, std::min<int64_t>(target, nbatch / 4));

@@ -1,5 +1,5 @@
 // libextrack_hip.so: lookup of the register-resident 2-state kernels (xt_reg2.h), instantiated per frame_len in extrack_reg2_f{4..7}.hip.
-// The launch sites live in extrack_hip.hip (extrack_loglik*) and extrack_grad.hip (extrack_loglik_grad).
+// The launch sites live in extrack_ll.hip (extrack_loglik*) and extrack_grad.hip (extrack_loglik_grad).
 const void* xt_r2_kernel_f4(int D, int K, int NP);
 const void* xt_r2_kernel_f5(int D, int K, int NP);
 const void* xt_r2_kernel_f6(int D, int K, int NP);

@@ -1,7 +1,7 @@
-// Host-side state of libextrack_hip.so shared by its translation units (extrack_hip.hip: context, buckets, fixed-window likelihood /
-// posteriors; extrack_th.hip: threshold-fusion likelihood / posteriors; extrack_refine.hip: position refinement; extrack_grad.hip:
-// likelihood + gradient; extrack_hist.hip: state-duration histograms; ...) and the device-side execution context the kernel bodies are
-// written against.
+// Host-side state of libextrack_hip.so shared by its translation units (extrack_hip.hip: context, buckets, model upload; extrack_ll.hip:
+// fixed-window likelihood / posteriors / sequence matrix; extrack_th.hip: threshold-fusion likelihood / posteriors; extrack_refine.hip:
+// position refinement; extrack_grad.hip: likelihood + gradient; extrack_hist.hip: state-duration histograms; ...) and the device-side
+// execution context the kernel bodies are written against.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -348,7 +348,7 @@ struct extrack_ctx {
     // Frozen plan (extrack_th_freeze_plan): threshold-fusion evaluations skip the plan kernel and follow the plan the last planning
     // evaluation left in the buckets; per launch group (keyed by its first bucket and size) the sequence counts that size the apply / gradient launch
     double* d_big_ws = nullptr;  // per-wavefront sequence state of the global-memory kernel for big models (xt_big.h)
-    size_t big_ws_cap = 0;       // doubles
+    size_t big_ws_cap = 0;       // bytes
     void* d_map_ws = nullptr;    // state-path decoder (xt_map.h): back-pointer words of the launched grid when they do not live in LDS
     size_t map_ws_cap = 0;       // bytes
     void* d_map_out = nullptr;   // ... its device outputs ([N] scores, [N][L] states), kept between calls
@@ -376,7 +376,7 @@ static const int XT_DESC_CAP = 4096;  // bucket descriptors per evaluation (buck
         }                                                                                       \
     } while (0)
 
-// shared host helpers (defined in extrack_hip.hip)
+// shared host helpers (defined in extrack_hip.hip; xt_max_grid and xt_reduce_partials in extrack_ll.hip)
 int xt_fail(extrack_ctx* ctx, int code, const std::string& msg);
 // Grow-only device buffer: when `bytes` exceeds *cap, waits for ctx->stream, frees *buf and allocates `alloc` bytes (0: `bytes`); with
 // `pinned`, a pinned host buffer of the same size is kept beside it.  A failed allocation reports "<what>: <HIP error>".
@@ -386,6 +386,7 @@ int xt_validate_model(extrack_ctx* ctx, const extrack_model* m);
 void xt_model_host(const extrack_model* m, XtModelHost& mh);
 int xt_upload_blob(extrack_ctx* ctx, const std::vector<double>& blob);   // -> ctx->d_blob (double-buffered staging)
 int xt_prepare_config(extrack_ctx* ctx, const extrack_model* m);         // digit-slot tables of (S, ns, F) -> ctx->cfg, d_base_tab, d_off_tab
+int xt_prepare(extrack_ctx* ctx, const extrack_model* m);                // ... + the model blob of a fixed-window evaluation -> ctx->blob_host, inline or uploaded
 int xt_reserve_partials(extrack_ctx* ctx, size_t n);
 size_t xt_desc_base(const extrack_ctx* ctx);
 size_t xt_max_grid(const extrack_ctx* ctx);

@@ -1,5 +1,5 @@
 // Track-likelihood / state-posterior recursion: the kernel body shared by the HIP kernels
-// (extrack_hip.hip) and by the CPU-thread emulator used in tests (tests/emul).
+// (extrack_ll.hip, extrack_gaps.hip) and by the CPU-thread emulator used in tests (tests/emul).
 //
 // What it computes (reference: extrack/tracking.py:109-318 P_Cs_inter_bound_stats, fixed window,
 // + extrack/tracking_0.py:440-458 Proba_Cs; exact statement in SURVEY.md Appendix A):

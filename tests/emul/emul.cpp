@@ -29,6 +29,7 @@
 #include "../../extrack_amd/csrc/xt_launch_split.h"
 #include "../../extrack_amd/csrc/xt_th_geom.h"
 #include "../../extrack_amd/csrc/xt_grad_geom.h"
+#include "../../extrack_amd/csrc/xt_ll_geom.h"
 
 struct EmulLauncher {
     XtKernelArgs a;
@@ -168,7 +169,7 @@ extern "C" int xt_emul_run(const double* tracks, const double* sigma, long long 
     l.a.min_len = min_len;
     l.a.locerr_mode = locerr_mode;
     l.a.KS = KS;
-    {   // the launcher's scaling decision for the 2-state fast path (extrack_hip.hip: xt_launch_group)
+    {   // the launcher's scaling decision for the 2-state fast path (extrack_ll.hip: xt_ll_scaling)
         double lo = INFINITY, hi = -INFINITY;
         if (locerr_mode == 0) {
             for (int k = 0; k < locerr_dims && k < 3; ++k) {
@@ -386,6 +387,24 @@ extern "C" int xt_emul_grad_pick(const long long* in, int n_cu, const long long*
     for (int i = 0; i < 24; ++i) out[i] = o[i];
     return 0;
 }
+
+// xt_ll_pick (csrc/xt_ll_geom.h).  in [13]: S, NS, F, D, K, KS, preds, seq, gaps, ll_reg2, force_big, budget_mb, nbuckets; n_cu; out [9]: the XtLlPick
+// fields in declaration order.  Returns -1 for a model xt_build_config refuses.  frame_len 16 is beyond xt_build_config (the library never gets
+// there): the scalar fields of the window one longer than 15, which is all the function reads - it keeps the "posteriors: frame_len > 15" guard.
+extern "C" int xt_emul_ll_pick(const long long* in, int n_cu, long long* out)
+{
+    static XtConfig c;  // kept between calls, as in xt_emul_grad_pick
+    if (c.S != in[0] || c.NS != in[1] || c.F != in[2]) {
+        if (in[2] == 16 && pow((double)in[0], 16.0) > 1048576.0) return -1;
+        if (!xt_build_config((int)in[0], (int)in[1], in[2] == 16 ? 15 : (int)in[2], c).empty()) return -1;
+        if (in[2] == 16) c.F = 16, c.E *= c.S, c.NG *= c.S, c.EP = xt_padded_entries(c.E, c.skew);
+    }
+    const XtLlPick p = xt_ll_pick(c, (int)in[3], (int)in[4], (int)in[5], in[6] != 0, in[7] != 0, in[8] != 0, (int)in[9], in[10] != 0, (size_t)in[11], (int)in[12], n_cu);
+    const long long o[9] = {p.path, p.refusal, p.tpb, p.threads, (long long)p.lds, p.wide, p.sel, p.ws_stride, (long long)p.max_blocks};
+    for (int i = 0; i < 9; ++i) out[i] = o[i];
+    return 0;
+}
+extern "C" const char* xt_emul_ll_refusal_text(int r) { return xt_ll_refusal_text(r); }
 
 // Several length buckets served by ONE emulated launch of the global-state body (csrc/xt_big.h), the way xt_launch_group launches it: grid
 // from xt_split_blocks(target, cap, ...) (or the explicit blocks_per_bucket when given), scratch for exactly cap blocks of NW wavefront

@@ -14,7 +14,7 @@ def lib():
         so = os.path.join(HERE, "libxt_emul.so")
         src = os.path.join(HERE, "emul.cpp")
         hdrs = [os.path.join(HERE, "..", "..", "extrack_amd", "csrc", h) for h in ("xt_kernel.h", "xt_math.h", "xt_tables.h", "xt_dispatch.h", "xt_th.h", "xt_entry.h", "xt_fast2.h", "xt_grad.h",
-                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h", "xt_launch_split.h", "xt_th_geom.h", "xt_grad_geom.h")]
+                                                                                             "xt_grad_host.h", "xt_thgrad.h", "xt_thgrad2.h", "xt_big.h", "xt_hist.h", "xt_hist_host.h", "xt_reg2.h", "xt_gradr.h", "xt_rev.h", "xt_seqmat.h", "xt_launch_split.h", "xt_th_geom.h", "xt_grad_geom.h", "xt_ll_geom.h")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in [src, os.path.join(HERE, "emul_r2.cpp"), os.path.join(HERE, "emul_gradr.cpp"), os.path.join(HERE, "emul_rev.cpp"), os.path.join(HERE, "emul_ctx.h")] + hdrs):
             import subprocess
             units = ["emul.cpp", "emul_r2.cpp", "emul_gradr.cpp", "emul_rev.cpp"]  # compiled side by side: emul_r2.cpp unrolls the whole step loop per instance
@@ -129,6 +129,21 @@ def grad_pick(args, n_cu, knobs):
     if lib().xt_emul_grad_pick((C.c_longlong * 11)(*[int(v) for v in args]), int(n_cu), (C.c_longlong * 8)(*[int(v) for v in knobs]), out) != 0:
         raise RuntimeError("xt_build_config refuses the model")
     return list(out)
+
+
+def ll_pick(args, n_cu):
+    """The fixed-window path's decision for one launch group (csrc/xt_ll_geom.h: xt_ll_pick): args = S, NS, F, D, K, KS, preds, seq, gaps, ll_reg2,
+    force_big, budget_mb, nbuckets -> the 9 XtLlPick fields in declaration order."""
+    out = (C.c_longlong * 9)()
+    if lib().xt_emul_ll_pick((C.c_longlong * 13)(*[int(v) for v in args]), int(n_cu), out) != 0:
+        raise RuntimeError("xt_build_config refuses the model")
+    return list(out)
+
+
+def ll_refusal_text(r):
+    f = lib().xt_emul_ll_refusal_text
+    f.restype = C.c_char_p
+    return f(int(r)).decode()
 
 
 def run_big_multi(buckets, locerr, ds, Fs, T, pBL, p_stay, ns, F, min_len, max_len, target, cap, blocks_per_bucket=None, preds=False):

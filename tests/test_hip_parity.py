@@ -549,3 +549,44 @@ def test_long_tracks_error_accumulation(S, F, L):
     _, _, preds = T.P_Cs_inter_bound_stats(Cs[:6], LE, ds, Fs, Tm, 0.1, 1, [1.0], 1, F, 1, 3)
     _, pref = O.p_cs_inter_bound_stats(Cs[:6], LE, ds, Fs, Tm, 0.1, 1, [1.0], 1, F, 1, 3)
     assert np.abs(preds - pref).max() < TOL_PRED
+
+
+@pytest.mark.parametrize("S,NS,F,what,env,path", [
+    (2, 1, 4, "loglik", {}, 1), (2, 1, 4, "loglik", dict(EXTRACK_LL_PATH="lds"), 2), (3, 1, 4, "loglik", {}, 4), (3, 1, 4, "predict", {}, 4),
+    (2, 1, 10, "loglik", {}, 4), (2, 2, 4, "loglik", {}, 3), (2, 1, 4, "gaps", {}, 5), (2, 1, 4, "seq", {}, 4), (2, 1, 12, "loglik", {}, 6),
+    (3, 1, 4, "loglik", dict(EXTRACK_FORCE_BIG="1"), 6)])
+def test_launcher_follows_the_pick_function(S, NS, F, what, env, path, monkeypatch):
+    """The launcher (csrc/extrack_ll.hip) runs what xt_ll_pick (csrc/xt_ll_geom.h) decides: every kernel family in a fresh context, two
+    buckets of 40 tracks (6 and 9 positions, D = 2), one global error - workgroup, LDS bytes and tracks per block of the last launch are
+    those of the matching row of tests/golden/ll_geom_parent.json (the recorded decision of the launcher before the function existed;
+    tests/test_ll_geom_cpu.py).  Every family's LDS bytes follow from the pick alone, so all three figures are compared on every case."""
+    import json
+    import os
+    from extrack_amd import _lib, engine, synth
+    from gap_reference import CELL, DT, MODELS, PBL
+    for k in ("EXTRACK_LL_PATH", "EXTRACK_FORCE_BIG", "EXTRACK_BIG_WS_MB"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    d = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ll_geom_parent.json")))
+    key = [S, NS, F, 2, 1, 0, int(what == "predict"), int(what == "seq"), int(what == "gaps"), 0 if env.get("EXTRACK_LL_PATH") == "lds" else 1,
+           int("EXTRACK_FORCE_BIG" in env), 32768, 1]
+    row = [r for r in d["rows"] if r[:13] == key]
+    assert len(row) == 1
+    want = dict(zip(d["out"], row[0][13:]))
+    assert want["path"] == path and (F != 10 or (want["wide"], want["threads"]) == (1, 512)), want
+    Ds, Tm, Fs = MODELS[S]
+    ds = np.sqrt(2 * Ds * DT)
+    model = _lib.ModelHandle(ds, Fs, Tm, engine.p_stay_table(ds, S, NS, CELL), PBL, NS, F, 3, 9, locerr=[0.02])
+    ctx = _lib.Context(0)
+    try:
+        for L in (6, 9):
+            tr = synth.brownian_tracks(40, L, list(Ds), Tm, list(Fs), seed=L)
+            ctx.upload_bucket(synth.drop_positions(tr, 0.25, seed=L) if what == "gaps" else tr, None)
+        out = (ctx.predict(model, 0) if what == "predict" else ctx.sequence_matrix(model, 0) if what == "seq" else
+               ctx.loglik(model, gaps=what == "gaps"))
+        info = ctx.last_launch_info()
+    finally:
+        ctx.close()
+    assert np.all(np.isfinite(out))
+    assert (info["threads"], info["lds_bytes"], info["tracks_per_block"]) == (want["threads"], want["lds"], want["tpb"]), (info, want)

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), "emul"))
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 
 N_CU = 256  # MI355X compute units
-NW_BIG = 4  # wavefronts per block of the global-state kernel (extrack_hip.hip: xt_launch_group)
+NW_BIG = 4  # wavefronts per block of the global-state kernel (extrack_ll.hip: xt_launch_group)
 
 
 def _E():
