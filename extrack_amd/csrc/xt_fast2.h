@@ -209,6 +209,26 @@ XT_HD T& xt_at(char* lds, int byte_off)
     return *(T*)(lds + byte_off);
 #endif
 }
+// Read of global memory at `base` (the same in every lane of the wavefront) + a 32-bit per-lane byte offset.  On the device through a
+// global-address-space pointer: a global_load with the base in scalar registers and one VGPR of offset, which counts on vmcnt only - the generic
+// pointer of a kernel argument's field gives a flat_load (64-bit per-lane address arithmetic, and every LDS wait waits for it as well).
+template <class T>
+XT_HD T xt_gld(const T* base, unsigned int byte_off)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(1))) char* gptr;
+    return *(const __attribute__((address_space(1))) T*)((gptr)(const char*)base + byte_off);
+#else
+    return *(const T*)((const char*)base + byte_off);
+#endif
+}
+// A 64-bit value that is the same in every lane, as cx.uniform makes an int one (scalar registers on the device)
+template <class Ctx>
+XT_HD int64_t xt_uniform64(Ctx& cx, int64_t v)
+{
+    const unsigned int lo = (unsigned int)cx.uniform((int)(unsigned int)((uint64_t)v & 0xffffffffu)), hi = (unsigned int)cx.uniform((int)(unsigned int)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
 XT_HD void xt_f2_check_lds_base(char* lds)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -356,6 +356,14 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 #define XT_R2_RC_H 0  // re-centring phase: a re-normalisation phase
 #endif
 #define XT_R2_RC_NONE (-2147483647 - 1)
+// Which likelihood-only instances stage complete batches through stage_ld / stage_st (xt_r2_body).  D = 3 keeps the loop alone: with the second
+// path its kernels spill ten more scalar registers and with them one more vector register (xt_ll_r2_kernel<6,3,1>: 28 -> 32 bytes of scratch).
+#ifndef XT_R2_STAGE_FAST
+#define XT_R2_STAGE_FAST(D) ((D) < 3)
+#endif
+#ifndef XT_R2_STAGE_GRP
+#define XT_R2_STAGE_GRP 4  // rounds of the wave whose loads are in flight together when a chunk is staged (xt_r2_body: stage)
+#endif
 // The [prev][q] table byte offset of a lane's first output, (prev * 2 + qa) * 8 (xt_r2_step), is a per-lane constant of the phase: all F - 1 of
 // them packed into one word, 5 bits per phase, built once per kernel.  The step extracts its field (the second output's offset is that ^ 8)
 // instead of deriving both from the lane id with shifts, ands and bit insertions in every step.
@@ -707,12 +715,69 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 
     const int64_t nbatch = (b.N + TPW - 1) / TPW;
     const int64_t W0 = (int64_t)lb * nwb + wib, NW = (int64_t)nb * nwb;
+    // likelihood only, scalar variance: the staging of complete batches below
+    constexpr bool FAST = NP == 0 && K == 1 && XT_R2_STAGE_FAST(D);
     for (int64_t batch = W0; batch < nbatch; batch += NW) {
         const int64_t trk = batch * TPW + ts;
         const bool act = trk < b.N;
 
+        // Staging of a chunk when every track of the batch exists (all but the last batch of a bucket; no per-peak errors): the batch's tracks
+        // are contiguous, so the chunk is read at ONE wave-uniform base + a 32-bit per-lane byte offset (xt_gld), formed from the lane id where
+        // it is used (nothing is kept across the step loop).  Loads (stage_ld: a position and the next one, for the delta, of up to
+        // XT_R2_STAGE_GRP rounds of the wave, all issued before any is used) come before the writes to LDS (stage_st): one wait for memory
+        // serves the chunk.
+        // Lanes without an element read the base: no branch around the loads.
+        constexpr int NE = TPW * XT_F2_CHUNK * D, NIT = (NE + 63) / 64, GRP = NIT < XT_R2_STAGE_GRP ? NIT : XT_R2_STAGE_GRP;
+        // element i of the chunk: track slot t_, ok: its position exists, nx: so does the next; returns the byte offset from the base
+        auto elem = [&](int p0, unsigned int i, unsigned int& t_, bool& ok, bool& nx) XT_INL {
+            t_ = i / (XT_F2_CHUNK * D);
+            const unsigned int r = i - t_ * (XT_F2_CHUNK * D), pp = (unsigned int)p0 + r / D;
+            ok = (NE % 64 == 0 || i < NE) && pp < (unsigned int)L;
+            nx = ok && pp + 1 < (unsigned int)L;
+            return ok ? (t_ * (unsigned int)(L * D) + r) * 8u : 0u;
+        };
+        auto stage_ld = [&](int64_t bt, int p0, int k0, double* v, double* vn) XT_INL {
+            const double* const base = b.tracks + xt_uniform64(cx, (bt * TPW * L + p0) * D);
+            const unsigned int ln = (unsigned int)xt_opaque(cx.lane()) & 63u;
+            XT_UNROLL
+            for (int g = 0; g < GRP; ++g) {
+                if (k0 + g >= NIT) continue;
+                unsigned int t_;
+                bool ok, nx;
+                const unsigned int off = elem(p0, ln + 64u * (k0 + g), t_, ok, nx);
+                v[g] = xt_gld(base, off);
+                vn[g] = xt_gld(base, off + (nx ? D * 8u : 0u));
+            }
+        };
+        auto stage_st = [&](int p0, int k0, const double* v, const double* vn) XT_INL {
+            const unsigned int posw = xt_r2_pos0(0) + wib * TPW * XT_F2_CHUNK * D * 8, ln = (unsigned int)xt_opaque(cx.lane()) & 63u;
+            XT_UNROLL
+            for (int g = 0; g < GRP; ++g) {
+                if (k0 + g >= NIT) continue;
+                const unsigned int i = ln + 64u * (k0 + g);
+                unsigned int t_;
+                bool ok, nx;
+                elem(p0, i, t_, ok, nx);
+                if (ok) {
+                    xt_at<double>(lds, (int)(posw + i * 8u)) = gform ? vn[g] - v[g] : v[g];  // g-form launches stage the deltas (see the loop below)
+                    if (v[g] != v[g]) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + (int)t_) * 4) = 1;
+                }
+            }
+        };
         auto stage = [&](int p0) XT_INL {
             cx.wave_sync();  // the reads of the previous chunk are done
+            if constexpr (FAST) {
+                if (KS == 0 && (batch + 1) * TPW <= b.N) {
+                    XT_UNROLL
+                    for (int k0 = 0; k0 < NIT; k0 += GRP) {
+                        double v[GRP], vn[GRP];
+                        stage_ld(batch, p0, k0, v, vn);
+                        stage_st(p0, k0, v, vn);
+                    }
+                    cx.wave_sync();
+                    return;
+                }
+            }
             for (int i = lane; i < TPW * XT_F2_CHUNK * D; i += 64) {
                 const int t_ = i / (XT_F2_CHUNK * D), r = i - t_ * (XT_F2_CHUNK * D);
                 const int64_t tk = batch * TPW + t_;
