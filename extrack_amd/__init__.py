@@ -2,7 +2,7 @@
 
 Public surface mirrors ``extrack.tracking`` for this path only:
 ``param_fitting``, ``predict_Bs``, ``cum_Proba_Cs``, ``extract_params``, ``generate_params``, ``get_params``,
-plus what the reference lacks: ``predict_states`` (most-likely state path per track), ``refine_along_states`` / ``get_pos_PDF_fixedBs`` (positions refined along such a path, ``extrack_amd.refined_localization``), ``parameter_uncertainties`` / ``track_scores`` (standard errors of a fit, ``extrack_amd.uncertainty``), ``gaps=True`` / ``extrack_amd.gaps.insert_gaps`` (tracks with missed detections: fit - ``gradient="forward"`` for the exact gap-aware gradient -, posteriors, state paths, the positions at the missed frames, and ``track_scores`` / ``parameter_uncertainties(..., gaps=True)`` for standard errors)
+plus what the reference lacks: ``predict_states`` (most-likely state path per track), ``refine_along_states`` / ``get_pos_PDF_fixedBs`` (positions refined along such a path, ``extrack_amd.refined_localization``), ``parameter_uncertainties`` / ``track_scores`` (standard errors of a fit, ``extrack_amd.uncertainty``), ``gaps=True`` / ``extrack_amd.gaps.insert_gaps`` (tracks with missed detections: fit - ``gradient="forward"`` for the exact gap-aware gradient -, posteriors, state paths, the positions at the missed frames, the state-duration histograms ``len_hist(..., gaps=True)``, and ``track_scores`` / ``parameter_uncertainties(..., gaps=True)`` for standard errors)
 (and ``extrack.histograms.len_hist`` in ``extrack_amd.histograms``).
 The recursion runs in hand-written HIP kernels behind the C ABI of ``include/extrack_hip.h``;
 importing this package does not touch the GPU, calling into it without the built library or without

@@ -23,6 +23,7 @@ EXPORTS = [
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
     "extrack_loglik_gaps", "extrack_predict_gaps", "extrack_map_states_gaps", "extrack_refine_fixed_states_gaps",
     "extrack_loglik_grad_gaps", "extrack_loglik_grad_gaps_async", "extrack_loglik_scores_gaps", "extrack_loglik_scores_gaps_async",
+    "extrack_segment_len_hist_gaps",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -124,6 +125,7 @@ def load():
     lib.extrack_loglik_scores_gaps.argtypes = lib.extrack_loglik_scores.argtypes
     lib.extrack_loglik_scores_gaps_async.argtypes = lib.extrack_loglik_scores_async.argtypes
     lib.extrack_segment_len_hist.argtypes = [vp, C.POINTER(ExtrackModel), i32, i32, vp]
+    lib.extrack_segment_len_hist_gaps.argtypes = lib.extrack_segment_len_hist.argtypes
     lib.extrack_refine_positions.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, vp]
     lib.extrack_refine_pos_pdf.argtypes = [vp, C.POINTER(ExtrackModel), i32, C.c_double, i32, vp, i64, vp, vp, vp]
     lib.extrack_refine_fixed_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp, vp, vp]
@@ -378,11 +380,13 @@ class Context:
                                                            C.c_void_p(d_out_ptr)))
         return n
 
-    def segment_len_hist(self, model, bucket_id, max_nb_states=500):
-        """State-duration histogram [len - 1, S] of one bucket (extrack/histograms.py:26-286 semantics, see include/extrack_hip.h)."""
+    def segment_len_hist(self, model, bucket_id, max_nb_states=500, gaps=False):
+        """State-duration histogram [len - 1, S] of one bucket (extrack/histograms.py:26-286 semantics, see include/extrack_hip.h).
+        ``gaps``: all-NaN rows are missed detections (extrack_segment_len_hist_gaps) instead of poisoning the bucket."""
         N, L, D, KS = self.buckets[bucket_id]
         out = np.zeros((L - 1, model.c.n_states))
-        self._check(self._lib.extrack_segment_len_hist(self._h, C.byref(model.c), int(bucket_id), int(max_nb_states), out.ctypes.data_as(C.c_void_p)))
+        fn = self._lib.extrack_segment_len_hist_gaps if gaps else self._lib.extrack_segment_len_hist
+        self._check(fn(self._h, C.byref(model.c), int(bucket_id), int(max_nb_states), out.ctypes.data_as(C.c_void_p)))
         return out
 
     def refine_positions(self, model, bucket_id, threshold=0.1, max_nb_states=1000):

@@ -160,7 +160,12 @@ XT_HD void xt_hist_sort_regs(Ctx& cx, double* key, int* idx, int NS2)
     }
 }
 
-template <int D, int K, class Ctx>
+// GAPS (missed detections): an interior row whose coordinates are all NaN is a frame without detection - the limit of
+// an infinite localisation error at that row.  Its step keeps the transition factor and the expansion by the new state, applies no Gaussian
+// factor, leaves the mean where it is and carries the variance unreduced; a ranking key drops the predictive density of a missing next
+// position (the same constant for every candidate in the limit).  One workgroup works on one track, so the test is uniform: a branch around
+// the reciprocal / logarithm / Gaussian of the step, never a select.  The history keeps one digit per frame, run lengths count frames.
+template <int D, int K, bool GAPS = false, class Ctx>
 XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
 {
     const int tid = cx.tid(), nt = cx.nthreads();
@@ -255,15 +260,33 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
         // ---- the whole track -> LDS
         if (tid == 0) flag[0] = 0;
         cx.sync();
-        for (int i = tid; i < L * D; i += nt) {
-            const double v = a.tracks[trk * L * D + i];
-            spos[i] = v;
-            if (v != v) flag[0] = 1;
-        }
-        for (int i = tid; i < L * KS; i += nt) {
-            const double v = a.sigma[trk * L * KS + i];
-            ssig[i] = v;
-            if (v != v) flag[0] = 1;
+        if (GAPS) {
+            // row by row: positions first; then a row is observed, missing as a whole (interior rows only) or poisons the track, and only
+            // the errors of observed rows are looked at (those of a gap row are copied and never read)
+            for (int i = tid; i < L * D; i += nt) spos[i] = a.tracks[trk * L * D + i];
+            cx.sync();
+            for (int r = tid; r < L; r += nt) {
+                int nn = 0;
+                for (int d = 0; d < D; ++d) nn += spos[r * D + d] != spos[r * D + d] ? 1 : 0;
+                if (nn != 0 && (nn != D || r == 0 || r == L - 1)) flag[0] = 1;
+            }
+            for (int i = tid; i < L * KS; i += nt) {
+                const double v = a.sigma[trk * L * KS + i];
+                const double c0 = spos[(i / KS) * D];
+                ssig[i] = v;
+                if (v != v && c0 == c0) flag[0] = 1;
+            }
+        } else {
+            for (int i = tid; i < L * D; i += nt) {
+                const double v = a.tracks[trk * L * D + i];
+                spos[i] = v;
+                if (v != v) flag[0] = 1;
+            }
+            for (int i = tid; i < L * KS; i += nt) {
+                const double v = a.sigma[trk * L * KS + i];
+                ssig[i] = v;
+                if (v != v) flag[0] = 1;
+            }
         }
         cx.sync();
         if (flag[0]) {  // NaN input: the track's histogram contribution is NaN, as in the reference
@@ -271,6 +294,8 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
             cx.sync();
             continue;
         }
+        // the gap flag of a position (unpoisoned track): the NaN of its staged first coordinate, the same value in every lane
+        auto gap_at = [&](int pos) { return GAPS && cx.uniform((int)(spos[pos * D] != spos[pos * D])) != 0; };
         double* cur = parA;
         double* nxt = parB;
         auto P_LP = [&](double* p) { return p; };
@@ -278,6 +303,14 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
         auto P_M = [&](double* p) { return p + 2 * (size_t)PC; };
         auto P_S = [&](double* p) { return p + (2 + D) * (size_t)PC; };
         auto P_H = [&](double* p) { return (uint64_t*)(p + (2 + D + K) * (size_t)PC); };
+        // step A of a missed frame: no Gaussian factor, the mean stays, the variance is carried unreduced (the child's s2 = d2 + s2)
+        auto carry_parents = [&](double* par, int np) {
+            for (int i = tid; i < np; i += nt) {
+                tLC[i] = 0.0;
+                for (int d = 0; d < D; ++d) tM[(size_t)d * PC + i] = P_M(par)[(size_t)d * PC + i];
+                for (int k = 0; k < K; ++k) tS[(size_t)k * PC + i] = P_S(par)[(size_t)k * PC + i];
+            }
+        };
 
         // ---- first position (histograms.py:93-138): S^2 sequences of two states, index i = old * S + new
         int n = S * S;
@@ -301,6 +334,9 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
         for (int c = 2; c <= L - 2; ++c) {
             const int p = c - 1;
             double lp[K], ln[K], cp[D], cn[D];
+            const bool gp = gap_at(p), gn = gap_at(p + 1);
+            // loaded for a missed frame too (NaN coordinates, possibly a NaN error), but then no kept value is computed from them: the branches
+            // below are on gp / gn.  Loading only the observed rows was measured to cost 28 - 108 bytes of scratch per lane more.
             l2_at(p, lp);
             l2_at(p + 1, ln);
             for (int d = 0; d < D; ++d) {
@@ -308,19 +344,23 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
                 cn[d] = spos[(p + 1) * D + d];
             }
             // A: per parent
-            for (int i = tid; i < n; i += nt) {
-                double m[D], s2[K], den[K];
-                for (int d = 0; d < D; ++d) m[d] = P_M(cur)[(size_t)d * PC + i];
-                for (int k = 0; k < K; ++k) {
-                    s2[k] = P_S(cur)[(size_t)k * PC + i];
-                    den[k] = lp[k] + s2[k];
+            if (gp) {
+                carry_parents(cur, n);
+            } else {
+                for (int i = tid; i < n; i += nt) {
+                    double m[D], s2[K], den[K];
+                    for (int d = 0; d < D; ++d) m[d] = P_M(cur)[(size_t)d * PC + i];
+                    for (int k = 0; k < K; ++k) {
+                        s2[k] = P_S(cur)[(size_t)k * PC + i];
+                        den[k] = lp[k] + s2[k];
+                    }
+                    tLC[i] = gauss(cp, m, den);
+                    for (int d = 0; d < D; ++d) {
+                        const int k = K == 1 ? 0 : d;
+                        tM[(size_t)d * PC + i] = (m[d] * lp[k] + cp[d] * s2[k]) / den[k];
+                    }
+                    for (int k = 0; k < K; ++k) tS[(size_t)k * PC + i] = lp[k] * s2[k] / den[k];
                 }
-                tLC[i] = gauss(cp, m, den);
-                for (int d = 0; d < D; ++d) {
-                    const int k = K == 1 ? 0 : d;
-                    tM[(size_t)d * PC + i] = (m[d] * lp[k] + cp[d] * s2[k]) / den[k];
-                }
-                for (int k = 0; k < K; ++k) tS[(size_t)k * PC + i] = lp[k] * s2[k] / den[k];
             }
             cx.sync();
             // B: per candidate j = i * S + r
@@ -332,6 +372,11 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
                     const int prev = (int)(P_H(cur)[i] & smask);
                     double m[D], v[K];
                     for (int d = 0; d < D; ++d) m[d] = tM[(size_t)d * PC + i];
+                    if (gn) {  // a missed next frame: its predictive density is the same constant for every candidate and is dropped
+                        key[j] = P_LP(cur)[i] + logT[prev * S + r] + tLC[i];
+                        idx[j] = j;
+                        continue;
+                    }
                     for (int k = 0; k < K; ++k) v[k] = d2t[prev * S + r] + tS[(size_t)k * PC + i] + ln[k];
                     key[j] = P_LP(cur)[i] + logT[prev * S + r] + tLC[i] + gauss(cn, m, v);
                     idx[j] = j;
@@ -422,7 +467,11 @@ XT_HD void xt_hist_body(const XtHistArgs& a, Ctx& cx)
         double ll[K], lq[K], cq[D], cl[D];
         l2_at(L - 1, ll);
         for (int d = 0; d < D; ++d) cl[d] = spos[(L - 1) * D + d];
-        if (expand) {
+        const bool gq = expand && gap_at(L - 2);
+        if (gq) {
+            carry_parents(cur, n);
+            cx.sync();
+        } else if (expand) {
             l2_at(L - 2, lq);
             for (int d = 0; d < D; ++d) cq[d] = spos[(L - 2) * D + d];
             for (int i = tid; i < n; i += nt) {

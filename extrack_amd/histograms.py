@@ -10,6 +10,11 @@ substep states into the per-position histories; with isBL it raises); the refere
 (chunk-wide shifts, histograms.py:191-192, 244-245) are replaced by a per-track normalisation; ``workers`` is accepted and ignored;
 the length buckets are taken in numeric key order (the reference takes the dict's insertion order and only works when that is
 ascending).
+
+``gaps=True`` (not in the reference): an interior row whose coordinates are all NaN is a frame without detection, as
+in ``param_fitting(gaps=True)`` - the tracks of ``extrack_amd.gaps.insert_gaps``, keyed by frame span.  The sequences are carried across
+such a frame by the transition alone, the histories keep one state per frame and the segment lengths are counted in frames
+(``extrack_segment_len_hist_gaps``).  Without the flag a NaN makes its bucket's histogram NaN as before.
 """
 import numpy as np
 
@@ -20,10 +25,13 @@ from .tracking import _resolve_device, extract_params
 __all__ = ["len_hist", "P_segment_len"]
 
 
-def P_segment_len(Cs, LocErr, ds, Fs, TrMat, min_l=3, pBL=0.1, isBL=1, cell_dims=[0.5], nb_substeps=1, max_nb_states=1000, device=0):
+def P_segment_len(Cs, LocErr, ds, Fs, TrMat, min_l=3, pBL=0.1, isBL=1, cell_dims=[0.5], nb_substeps=1, max_nb_states=1000, device=0, gaps=False):
     """Mirror of extrack/histograms.py:26-286 for one chunk.  Returns ``(None, None, seg_len_hist)``: the reference's first two return
     values (the per-sequence log-probabilities and state histories of the surviving sequences) never leave the GPU.
-    ``seg_len_hist[k - 1, s]`` = expected number of segments of k consecutive positions in state s, summed over the chunk."""
+    ``seg_len_hist[k - 1, s]`` = expected number of segments of k consecutive positions in state s, summed over the chunk.
+    ``gaps``: all-NaN interior rows of ``Cs`` are missed frames (the first and the last row of every track observed, a row finite or NaN as
+    a whole: checked on the host, ValueError); ``len`` is the frame span and segment lengths count frames; per-peak errors of the missed
+    rows are not read."""
     if nb_substeps != 1:
         raise NotImplementedError("state-duration histograms are built for nb_substeps == 1")
     Cs = np.asarray(Cs, dtype=np.float64)
@@ -40,24 +48,28 @@ def P_segment_len(Cs, LocErr, ds, Fs, TrMat, min_l=3, pBL=0.1, isBL=1, cell_dims
     if per_peak and LocErr.shape[0] != Cs.shape[0]:
         LocErr = np.broadcast_to(LocErr, (Cs.shape[0],) + LocErr.shape[1:])
     cell_dims = [c for c in np.atleast_1d(np.array(cell_dims, dtype=object)) if c is not None]
-    ts = TrackSet([Cs], [LocErr] if per_peak else None, device=device, min_len=max(int(min_l), 1), max_len=(L + 1 if isBL else L))
+    ts = TrackSet([Cs], [LocErr] if per_peak else None, device=device, min_len=max(int(min_l), 1), max_len=(L + 1 if isBL else L), gaps=gaps)
     try:
         model = ts.make_model(None if per_peak else LocErr, ds, Fs, TrMat, pBL, cell_dims, 1, 2)
         model.c.min_len = int(min_l)
-        return None, None, ts.ctx.segment_len_hist(model, 0, max_nb_states)
+        return None, None, (ts.ctx.segment_len_hist(model, 0, max_nb_states, gaps=True) if gaps else ts.ctx.segment_len_hist(model, 0, max_nb_states))
     finally:
         ts.close()
 
 
 def len_hist(all_tracks, params, dt, cell_dims=[0.5, None, None], nb_states=2, max_nb_states=500, workers=1, nb_substeps=1, input_LocErr=None,
-             device=None, comm=None):
+             device=None, comm=None, gaps=False):
     """State-duration histograms of a length-bucketed dataset (extrack/histograms.py:294-373): ``seg_len_hists[k - 1, s]`` = expected
     number of segments of k consecutive positions in state s over all tracks; shape [longest track length, nb_states].
     The longest bucket is the one whose tracks did not disappear (isBL = 0, histograms.py:335-338); ``min_l`` is the smallest key.
     ``comm`` (extrack_amd.distributed.Comm): every rank processes its row range of every bucket, the histograms are summed over
-    the ranks (one all-reduce of the small array)."""
+    the ranks (one all-reduce of the small array).
+    ``gaps``: the buckets are keyed by frame span and hold all-NaN rows at the missed frames (``extrack_amd.gaps.insert_gaps``); one GPU
+    (``comm`` must be None)."""
     if nb_substeps != 1:
         raise NotImplementedError("state-duration histograms are built for nb_substeps == 1")
+    if gaps and comm is not None:
+        raise NotImplementedError("missed detections (gaps=True) are not built for distributed evaluation: comm must be None")
     device = _resolve_device(device, comm)
     keys, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
     if not tracks:
@@ -76,7 +88,7 @@ def len_hist(all_tracks, params, dt, cell_dims=[0.5, None, None], nb_states=2, m
         sigmas = None if sigmas is None else [sigmas[i] for i in keep]
     out = np.zeros((max_l, S))
     if tracks:
-        ts = TrackSet(tracks, sigmas, device=device, min_len=min_l, max_len=max_l)
+        ts = TrackSet(tracks, sigmas, device=device, min_len=min_l, max_len=max_l, gaps=gaps)
         try:
             if sigmas is not None:
                 so = (params["slope_LocErr"].value, params["offset_LocErr"].value) if "slope_LocErr" in params else None
@@ -85,7 +97,7 @@ def len_hist(all_tracks, params, dt, cell_dims=[0.5, None, None], nb_states=2, m
                 model = ts.make_model(LocErr[0], ds, Fs, TrMat, pBL, cell, 1, 2)
             print("number of chunks:", int(sum(np.ceil(len(b) / 50) for b in tracks)))
             for i, b in enumerate(tracks):
-                h = ts.ctx.segment_len_hist(model, i, max_nb_states)
+                h = ts.ctx.segment_len_hist(model, i, max_nb_states, gaps=True) if gaps else ts.ctx.segment_len_hist(model, i, max_nb_states)
                 out[:h.shape[0]] += h
         finally:
             ts.close()

@@ -32,6 +32,8 @@
  *   extrack_segment_len_hist
  *       P_segment_len(...)[2] (extrack/histograms.py:26-286) summed over one bucket: the state-duration histogram that len_hist
  *       (histograms.py:294-373) accumulates over chunks of 50 tracks.
+ *   extrack_segment_len_hist_gaps
+ *       extrack_segment_len_hist for tracks with missed detections (all-NaN rows, as extrack_loglik_gaps): nothing in the reference.
  *   extrack_refine_positions
  *       get_pos_PDF + the weighted read-out of position_refinement for one bucket (extrack/refined_localization.py:207-338).
  *   extrack_refine_pos_pdf
@@ -313,6 +315,17 @@ int extrack_last_grad_ms(extrack_ctx* ctx, float* ms);
  * Limits: len * bits_per_state <= 4096 (bits = 1 / 2 / 3 for <= 2 / 4 / 8 states), max_nb_states * n_states <= 16384, and the staged track +
  * candidate arrays + histogram must fit the 160 KiB LDS of a CU (refused with EXTRACK_E_UNSUPPORTED otherwise). */
 int extrack_segment_len_hist(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int32_t max_nb_states, double* hist);
+/* The same for tracks with missed detections: an interior row whose coordinates are all NaN is a frame without detection (the limit of an
+ * infinite localisation error at that row, as extrack_loglik_gaps), and the bucket's len is the frame span.  At such a row the sequences
+ * are expanded by the new state and take its transition factor, but no Gaussian factor; the mean stays and the variance is carried
+ * unreduced; a ranking key drops the predictive density of a missed next frame.  The state histories keep one digit per frame and run
+ * lengths are counted in frames, missed ones included; min_len, isBL and the stay-in-field-of-view terms follow from len as above.  The
+ * per-peak error of a gap row is never read (NaN allowed).  The first and the last row must be observed and a row is finite or NaN as a
+ * whole: a track that breaks this, or has a NaN error at an observed row, makes the bucket's histogram NaN (as any NaN does in
+ * extrack_segment_len_hist).  Same arguments, limits and error codes as extrack_segment_len_hist; gap-free data gives the same bits.
+ * Inside a run of two or more missed frames distinct histories tie exactly; with pruning the order of such ties is decided by rounding
+ * and, through the last-K quirk of the reference's LL terms, visible in the result. */
+int extrack_segment_len_hist_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int32_t max_nb_states, double* hist);
 
 /* Refined positions of one bucket (extrack/refined_localization.py:304-338 position_refinement -> get_pos_PDF :207 -> get_LC_Km_Ks :48):
  * mu host [n][len][dims], sigma host [n][len].  Two passes of the threshold-fusion recursion (merge decisions from the first 30
