@@ -50,6 +50,13 @@ extern "C" int extrack_create(int device_id, extrack_ctx** out)
         }
     }
     if (const char* ev = getenv("EXTRACK_LL_PATH")) c->ll_reg2 = strcmp(ev, "reg2") == 0 ? 1 : (strcmp(ev, "lds") == 0 ? 0 : c->ll_reg2);
+    if (const char* ev = getenv("EXTRACK_GAP_REG2_F")) {  // "all" or a list of frame lengths out of 4..7
+        int mask = 0;
+        if (strcmp(ev, "all") == 0) mask = 0xf0;
+        for (const char* p = ev; *p; ++p)
+            if (*p >= '4' && *p <= '7') mask |= 1 << (*p - '0');
+        c->gap_reg2_fmask = mask;
+    }
     XtGradKnobs& gk = c->grad_knobs;
     gk.oversub = c->oversub;
     if (const char* ev = getenv("EXTRACK_GRAD_PATH")) {

@@ -1,7 +1,7 @@
 // libextrack_hip.so: the fixed-window likelihood / posterior / sequence-matrix path - kernel wrappers of xt_kernel.h, xt_fast2.h, xt_entry.h and
 // xt_big.h, the launcher (xt_launch_group, in stages), xt_gaps_check and the extrack_loglik* / extrack_predict* / extrack_sequence_* entry
-// points.  The path choice and launch geometry come from the host-only xt_ll_pick (xt_ll_geom.h); context, buckets and the model upload live
-// in extrack_hip.hip.  DESIGN.md section 23.
+// points.  The path choice and launch geometry come from the host-only xt_ll_pick and, for gapped two-state groups, xt_ll_gap_reg2
+// (xt_ll_geom.h); context, buckets and the model upload live in extrack_hip.hip.  DESIGN.md sections 23 and 25.
 #include "xt_host.h"
 
 #include "xt_dispatch.h"
@@ -168,6 +168,7 @@ static void xt_ll_args(extrack_ctx* ctx, const extrack_model* m, const std::vect
     memset(&a, 0, sizeof(a));
     xt_fill_args_from_config(ctx->cfg, a);
     if (l.pk.path == XT_LL_REG2 || l.pk.path == XT_LL_FAST2) a.well_scaled = xt_ll_scaling(ctx, m, bks, l.K);
+    if (l.pk.path == XT_LL_GAPS_REG2) a.well_scaled = 2;  // what xt_ll_gap_reg2 upgraded on
     if (ctx->blob_inline) {
         a.blob = nullptr;
         memcpy(a.blob_inline, ctx->blob_host.data(), ctx->blob_host.size() * sizeof(double));
@@ -216,6 +217,7 @@ static const void* xt_ll_kernel(const XtLlPick& pk, int D, int K, bool preds)
     XtLlKernelOf k{pk.wide, pk.path == XT_LL_REG2};
     if (pk.path == XT_LL_BIG) return xt_big_kernel_dk(D, K, preds);
     if (pk.path == XT_LL_GAPS) return xt_gap_kernel_ptr(pk.sel, D, K, preds, pk.wide);
+    if (pk.path == XT_LL_GAPS_REG2) return xt_r2_gap_kernel(pk.sel, D);
     if (pk.path == XT_LL_REG2 || pk.path == XT_LL_FAST2) xt_dispatch_f2(pk.sel, D, K, k);
     else if (pk.path == XT_LL_ENTRY) xt_dispatch_entry(pk.sel, D, K, k);
     else xt_dispatch(pk.sel, D, K, preds, k);
@@ -291,8 +293,16 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     const bool force_big = ev && atoi(ev) != 0;
     size_t budget_mb = 32 * 1024;
     if ((ev = getenv("EXTRACK_BIG_WS_MB"))) budget_mb = (size_t)std::max(16, atoi(ev));
-    const XtLlPick& pk = l.pk = xt_ll_pick(ctx->cfg, l.D, l.K, m->locerr_mode ? b0.KS : 0, l.preds, l.d_seq != nullptr, l.gaps, ctx->ll_reg2, force_big,
-                                           budget_mb, (int)bks.size(), ctx->n_cu);
+    l.pk = xt_ll_pick(ctx->cfg, l.D, l.K, m->locerr_mode ? b0.KS : 0, l.preds, l.d_seq != nullptr, l.gaps, ctx->ll_reg2, force_big, budget_mb,
+                      (int)bks.size(), ctx->n_cu);
+    if (l.pk.path == XT_LL_GAPS && !l.preds && xt_use_reg2(ctx->cfg.S, ctx->cfg.NS, ctx->cfg.F)) {
+        // missed detections, two states: the register-resident kernel where its g-form steps are valid (xt_ll_gap_reg2), else the general gap body
+        int Lmax = 0;
+        for (const XtBucket* b : bks) Lmax = std::max(Lmax, b->L);
+        l.pk = xt_ll_gap_reg2(l.pk, ctx->cfg, l.D, l.K, m->locerr_mode ? b0.KS : 0, l.preds, l.per_track, ctx->ll_reg2, xt_ll_scaling(ctx, m, bks, l.K), Lmax,
+                              ctx->blob_host.size() > 8 ? ctx->blob_host[7] : NAN, ctx->gap_reg2_fmask);
+    }
+    const XtLlPick& pk = l.pk;
     if (pk.path == XT_LL_NONE) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, xt_ll_refusal_text(pk.refusal));
     xt_ll_descs(m, bks, l);
     xt_ll_args(ctx, m, bks, l);
@@ -309,6 +319,7 @@ static int xt_launch_group(extrack_ctx* ctx, const extrack_model* m, const std::
     if (e == hipSuccess) e = xt_ll_enqueue(ctx, kp, l);
     if (e != hipSuccess) return xt_fail(ctx, EXTRACK_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     xt_set_launch_info(ctx, l.grid, pk.threads, pk.lds, pk.tpb, l.occ);
+    ctx->last_ll_path = pk.path;
     *grid_out = l.grid;
     return EXTRACK_OK;
 }
@@ -447,6 +458,13 @@ static int xt_predict_sync(extrack_ctx* ctx, const extrack_model* m, int32_t buc
         if (e != hipSuccess) rc = xt_fail(ctx, EXTRACK_E_HIP, std::string("predict: ") + hipGetErrorString(e));
     }
     return rc;
+}
+
+extern "C" int extrack_last_ll_path(const extrack_ctx* ctx, int32_t* path)
+{
+    if (!ctx || !path) return EXTRACK_E_INVALID;
+    *path = ctx->last_ll_path;
+    return EXTRACK_OK;
 }
 
 extern "C" int extrack_predict(extrack_ctx* ctx, const extrack_model* m, int32_t bucket_id, double* preds)

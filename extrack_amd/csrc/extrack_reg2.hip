@@ -15,3 +15,17 @@ const void* xt_r2_kernel(int F, int D, int K, int NP)
     if (F == 7) return xt_r2_kernel_f7(D, K, NP);
     return nullptr;
 }
+
+// The gap-aware likelihood-only kernels (extrack_reg2_gaps_f{4..7}.hip): kernel address for (frame_len, dims); one global localisation error.
+const void* xt_r2_gap_kernel_f4(int D);
+const void* xt_r2_gap_kernel_f5(int D);
+const void* xt_r2_gap_kernel_f6(int D);
+const void* xt_r2_gap_kernel_f7(int D);
+const void* xt_r2_gap_kernel(int F, int D)
+{
+    if (F == 4) return xt_r2_gap_kernel_f4(D);
+    if (F == 5) return xt_r2_gap_kernel_f5(D);
+    if (F == 6) return xt_r2_gap_kernel_f6(D);
+    if (F == 7) return xt_r2_gap_kernel_f7(D);
+    return nullptr;
+}

@@ -251,6 +251,7 @@ struct extrack_ctx {
     int n_cu = 0;
     int oversub = 8;  // block generations per CU (EXTRACK_OVERSUB overrides; tuning knob)
     int ll_reg2 = 1;  // 2-state likelihood: 1 = register-resident kernel (xt_reg2.h), 0 = LDS-resident (xt_fast2.h); EXTRACK_LL_PATH=reg2|lds
+    int gap_reg2_fmask = 0xe0;  // missed detections: frame lengths (bit F) whose two-state likelihood launches go to the gap-aware register-resident kernel (xt_ll_geom.h: XT_LL_GAP_REG2_F_DEFAULT = 5, 6, 7); EXTRACK_GAP_REG2_F=4,5,6,7 | all
     XtGradKnobs grad_knobs;  // path choice and geometry of the gradient launches (xt_grad_geom.h: EXTRACK_GRAD_PATH, EXTRACK_GRADR_NPC, EXTRACK_REV_LOG_MB, ...)
     double* d_revlog = nullptr;  // merged-state logs of the reverse-mode kernels
     size_t revlog_cap = 0;       // doubles
@@ -315,6 +316,7 @@ struct extrack_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int32_t launch_info[6] = {0, 0, 0, 0, 0, 0};
+    int last_ll_path = 0;  // XtLlPath of the last likelihood / posterior / sequence-matrix launch group (extrack_last_ll_path), 0 before any
     std::map<std::pair<const void*, std::pair<int, size_t>>, int> occ_cache;
     int th_capE = 128;          // plan capacity (expanded sequences per step); grows on overflow
     int th_learnP = 0, th_learnE = 0;  // live parent / expanded sequence counts seen by the last plan (+ headroom): LDS workspace sizing
@@ -442,6 +444,7 @@ inline std::vector<std::vector<XtBucket*>> xt_launch_groups(extrack_ctx* ctx, si
 }
 __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, double* __restrict__ out);
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built
+const void* xt_r2_gap_kernel(int F, int D);  // extrack_reg2.hip: gap-aware register-resident 2-state likelihood kernels (one global error), nullptr = not built
 const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide);  // extrack_gaps.hip: gap-aware instantiations of xt_track_body (wide: more than 256 threads), nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers
 // threshold-fusion plan stage for other translation units (extrack_th.hip): `cb` gets, per launch group, the kernel arguments with the plan

@@ -1,5 +1,7 @@
 // Register-resident path of the track-likelihood recursion for TWO-STATE models with one substep (S = 2, ns = 1,
 // frame_len 4..7): log-likelihood (NP = 0) and log-likelihood + exact gradient along NP model directions (NP > 0).
+// GAPS (compile-time, default off: the instantiations without it are unchanged): the likelihood-only g-form path with missed detections
+// (all-NaN rows, DESIGN.md sections 18 and 25) - see xt_r2_step_g, xt_r2_chain_g and the staging in xt_r2_body.
 //
 // Reference: extrack/tracking.py:109-318 (P_Cs_inter_bound_stats), :76-98 (log_integrale_dif), :361-423 (fuse_tracks_general);
 // the gradient replaces the finite differences lmfit's BFGS takes around cum_Proba_Cs (tracking.py:1371).  Same mathematics as
@@ -62,6 +64,11 @@ XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw)
 {
     return xt_r2_acc0(NP, D, KS, tpw) + XT_F2_WAVES * 8 * (NP + 3) * 8 + (NP == 0 ? 2 * XT_R2_RC_ARR + XT_F2_WAVES * 8 * 8 : 0);
 }
+// Gap-aware likelihood-only launches (xt_r2_body<.., GAPS = true>), after everything above: per (wave, slot) 16 bytes -
+// {u32 rows of the staged chunk with a NaN coordinate, then: rows that are missed frames; u32 rows with a finite coordinate; int last observed
+// row before the chunk; int missed rows of the track so far}
+XT_HD int xt_r2_gap0(int D, int tpw) { return xt_r2_block_bytes(0, D, 0, tpw); }
+XT_HD int xt_r2_gap_block_bytes(int D, int tpw) { return xt_r2_gap0(D, tpw) + XT_F2_WAVES * 8 * 16; }
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
 // Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
 // ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2) (kept in the map; the ratio form of the step no longer reads it), 2 l2} and LT2[v][prev][q] = -2 lnT' = -2 (ln TAB[v][prev][q] - D/2 ln l2), v = 0 (T), 1 (T * stay)
@@ -404,8 +411,13 @@ XT_HD int xt_r2_tid8(Ctx& cx)
     return cx.tid() * 8;
 #endif
 }
-template <int F, int D, int H, bool FIRST = false, class Ctx>
-XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int& pk, int tab, const double* dc)
+// GAPS (missed detections): `gap` = position t of this lane's track is a missed frame.  The l2 -> infinity limit of the step
+// above: g_q -> 0 in the update of the mean (m_q = m_bar, so r_q = r_bar + dc: k_q = 1 / Ws), l2 s2 / (l2 + s2) -> s2 (v_q = v_bar + d2_q =
+// Dq_q / Ws), no Gaussian factor (y_q = Wm, no esq h_q in lambda).  1 / Ws = R Dq0 Dq1 comes out of the shared reciprocal.  lambda keeps the
+// table's -2 lnT' = -2 lnT + D ln l2: every sequence of a track passes the same gaps, so the D/2 ln l2 per gap is a per-track constant that the
+// read-out gives back together with the gap's share of log 2 pi (xt_r2_body).  Per-lane selects on top of the observed step: no branch.
+template <int F, int D, int H, bool FIRST = false, bool GAPS = false, class Ctx>
+XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int& pk, int tab, const double* dc, bool gap = false)
 {
     constexpr int NGB = F - 1;
     constexpr int XB = xt_r2_gbit(F, H);
@@ -466,14 +478,32 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[
     const double l2W = FIRST ? l2 : l2 * Ws;
     const double WmW = FIRST ? Wm : Wm * Ws;
     double ny[2], nl[2], nr[2][D], nv[2];
-    XT_UNROLL
-    for (int q = 0; q < 2; ++q) {
-        const double k = l2W * h[q];
-        ny[q] = D == 2 ? WmW * k : Wm * xt_pow_half<D>(FIRST ? k : Ws * k);
-        nl[q] = xt_fma(esq, h[q], LT[q]) + base;
+    if constexpr (GAPS) {
+        const double Dq[2] = {Dq0, Dq1};
+        const double rW = FIRST ? 1.0 : R * (Dq0 * Dq1);  // 1 / Ws
+        const double esqg = gap ? 0.0 : esq;
         XT_UNROLL
-        for (int d = 0; d < D; ++d) nr[q][d] = xt_fma(ed[d], k, dc[d]);
-        nv[q] = xt_fma(-l2W, k, l22);
+        for (int q = 0; q < 2; ++q) {
+            const double ko = l2W * h[q];
+            const double k = gap ? rW : ko;
+            const double yo = D == 2 ? WmW * ko : Wm * xt_pow_half<D>(FIRST ? ko : Ws * ko);
+            ny[q] = gap ? Wm : yo;
+            nl[q] = xt_fma(esqg, h[q], LT[q]) + base;
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) nr[q][d] = xt_fma(ed[d], k, dc[d]);
+            const double vo = xt_fma(-l2W, ko, l22);
+            nv[q] = gap ? Dq[q] * rW : vo;
+        }
+    } else {
+        XT_UNROLL
+        for (int q = 0; q < 2; ++q) {
+            const double k = l2W * h[q];
+            ny[q] = D == 2 ? WmW * k : Wm * xt_pow_half<D>(FIRST ? k : Ws * k);
+            nl[q] = xt_fma(esq, h[q], LT[q]) + base;
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) nr[q][d] = xt_fma(ed[d], k, dc[d]);
+            nv[q] = xt_fma(-l2W, k, l22);
+        }
     }
     cx.template pair_exchange<XB>(ny[0], ny[1]);
     cx.template pair_exchange<XB>(nl[0], nl[1]);
@@ -497,8 +527,9 @@ XT_HD void xt_r2_step_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[
 // positions: y >= 1e-120 times the initial fraction.  The first full step and the merges after it form W^3-sized products, so the chain hands
 // over a normalised mantissa: ONE frexp at its end, its exponent folded into lambda.  Lanes whose digits are still dummies (a bucket too
 // short to fill the window) end at y = 0 with finite lambda, r, v; such a bucket goes from here straight to the read-out.
-template <int F, int D, class Ctx, class GetPos>
-XT_HD void xt_r2_chain_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int T, int stay_from, GetPos& getpos)
+// GAPS: bit t of gm = position t of this lane's track is a missed frame - g = 1 in the mean, v = v + d2, no factor (xt_r2_step_g), per-lane selects.
+template <int F, int D, bool GAPS = false, class Ctx, class GetPos>
+XT_HD void xt_r2_chain_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)[2], int T, int stay_from, GetPos& getpos, unsigned int gm = 0u)
 {
     constexpr int NGB = F - 1;
     const int lane = xt_opaque(cx.lane());
@@ -519,11 +550,20 @@ XT_HD void xt_r2_chain_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)
         double rsq = 0.0;
         XT_UNROLL
         for (int d = 0; d < D; ++d) rsq = xt_fma(s.m[0][d], s.m[0][d], rsq);
-        y *= xt_pow_half<D>(g);
-        la = xt_fma(rsq, rd, la + LT);
-        v = xt_fma(-l2, g, l22);
-        XT_UNROLL
-        for (int d = 0; d < D; ++d) s.m[0][d] = xt_fma(s.m[0][d], g, dc[d]);
+        if constexpr (GAPS) {
+            const bool gap = (gm >> t) & 1u;
+            y *= gap ? 1.0 : xt_pow_half<D>(g);
+            la = xt_fma(gap ? 0.0 : rsq, rd, la + LT);
+            v = gap ? d2 + v : xt_fma(-l2, g, l22);
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) s.m[0][d] = xt_fma(s.m[0][d], gap ? 1.0 : g, dc[d]);
+        } else {
+            y *= xt_pow_half<D>(g);
+            la = xt_fma(rsq, rd, la + LT);
+            v = xt_fma(-l2, g, l22);
+            XT_UNROLL
+            for (int d = 0; d < D; ++d) s.m[0][d] = xt_fma(s.m[0][d], g, dc[d]);
+        }
     }
     int dummy = 0;  // lane bits of digits that are still dummies (time < 0)
     XT_UNROLL
@@ -629,9 +669,12 @@ XT_HD void xt_r2_chain(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int T, int sta
 }
 
 // NP == 0: log-likelihood only, per-block sums to a.partials (ga unused).  NP > 0: ga.gpartials[block][1 + NP] = {sum LL, sum dLL/dtheta_p}.
-template <int F, int D, int K, int NP, int VAR = 0, class Ctx>
+// GAPS (likelihood only, K == 1, launches the host found fit for g-form steps: xt_ll_gap_reg2, xt_ll_geom.h): an all-NaN row is a missed frame
+// (DESIGN.md sections 18, 25); LDS of xt_r2_gap_block_bytes.
+template <int F, int D, int K, int NP, int VAR = 0, bool GAPS = false, class Ctx>
 XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 {
+    static_assert(!GAPS || (NP == 0 && K == 1), "the gap-aware instantiation is the likelihood-only g-form path");
     int lb, nb;
     const XtBucketDesc b = xt_bind_bucket(a, cx.block(), cx.nblocks(), lb, nb);
     typedef XtR2Geom<F> Gm;
@@ -660,7 +703,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     xt_f2_check_lds_base(lds);
     xt_f2_build_exp_table(cx, lds, XT_F2_EXPB_OFF, (const double*)(lds + XT_F2_T64_OFF));  // the 1024-entry table of xt_exp_tab_x2 from the blob's 64 entries
     // g-form steps (xt_r2_step_g): the launcher found one global localisation variance l2 >= 1e-12 in a well-scaled launch (well_scaled == 2)
-    const bool gform = NP == 0 && K == 1 && a.well_scaled == 2 && a.locerr_mode == 0;
+    const bool gform = GAPS || (NP == 0 && K == 1 && a.well_scaled == 2 && a.locerr_mode == 0);
     if constexpr (NP == 0 && K == 1) {
         if (gform && cx.tid() < 10) {
             const int i = cx.tid();
@@ -668,7 +711,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             if (i < 8)
                 xt_at<double>(lds, XT_R2_LNT_OFF + i * 8) = -2.0 * (log(smem[XT_BLOB_HDR + i]) - 0.5 * D * log(l2));
             else
-                xt_at<double>(lds, XT_R2_GC_OFF + (i - 8) * 8) = i == 8 ? -0.5 / l2 : 2.0 * l2;
+                xt_at<double>(lds, XT_R2_GC_OFF + (i - 8) * 8) = i == 8 ? (GAPS ? 0.5 * D * (XT_LOG2PI + log(l2)) : -0.5 / l2) : 2.0 * l2;  // GAPS: what the read-out gives back per missed row
         }
     }
     cx.sync();
@@ -685,7 +728,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     // g-form steps: the [prev][q] table offsets of this lane's outputs in all F - 1 phases (xt_r2_pack_io), kept across the step loop instead of
     // the lane id
     int pk = xt_r2_pack_io<F, 0, Ctx>(lane);
-    const bool well_scaled = a.well_scaled != 0;
+    const bool well_scaled = GAPS || a.well_scaled != 0;
     const bool chain = NP == 0 && well_scaled;  // warm-up as per-lane chains (xt_r2_chain)
 
     double* pos = (double*)(lds + xt_r2_pos0(NPT)) + wib * TPW * XT_F2_CHUNK * (D + KS);  // [TPW][CHUNK][D]
@@ -766,6 +809,78 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
         auto stage = [&](int p0) XT_INL {
             cx.wave_sync();  // the reads of the previous chunk are done
+            if constexpr (GAPS) {
+                // Missed frames: a row is classified from ALL its coordinates (they may sit in different lanes, even rounds), so the chunk is
+                // staged in two passes around two row masks per track (LDS atomics).  Pass 1 loads every element and its successor and ORs the
+                // element's row into the NaN or the finite mask.  Pass 2 stages the deltas of the FILLED track: a missed row stands in as the last
+                // observed row before it (found in the masks; before the chunk: the row index carried in the track's cell, read again from
+                // memory), so the delta INTO a missed row is 0 and the one out of it reaches back to that row.  A NaN successor is a missed row
+                // or poisons its track where it is staged itself.  Serves complete and partial batches (the empty slots of the last batch
+                // mirror the bucket's last track); one wave-uniform base + 32-bit offsets.
+                const int gc0 = xt_r2_gap0(D, TPW) + wib * 8 * 16;
+                const unsigned int ln = (unsigned int)xt_opaque(cx.lane()) & 63u;
+                if (ln < 8u) {
+                    xt_at<uint32_t>(lds, gc0 + (int)ln * 16) = 0u;
+                    xt_at<uint32_t>(lds, gc0 + (int)ln * 16 + 4) = 0u;
+                }
+                cx.wave_sync();
+                const int64_t left = b.N - batch * TPW;
+                const unsigned int tmax = left < TPW ? (unsigned int)left - 1u : (unsigned int)TPW - 1u;
+                const double* const base = b.tracks + xt_uniform64(cx, batch * TPW * L * D);
+                auto gelem = [&](unsigned int i, unsigned int& t_, unsigned int& row, unsigned int& pp, unsigned int& o0) XT_INL {
+                    t_ = i / (XT_F2_CHUNK * D);
+                    const unsigned int r = i - t_ * (XT_F2_CHUNK * D);
+                    row = r / D;
+                    pp = (unsigned int)p0 + row;
+                    const unsigned int tc = t_ < tmax ? t_ : tmax;
+                    o0 = (tc * (unsigned int)L * D + (r - row * D)) * 8u;  // the element's coordinate in row 0 of its track
+                    return (NE % 64 == 0 || i < NE) && pp < (unsigned int)L;
+                };
+                double v[NIT], vn[NIT];
+                XT_UNROLL
+                for (int k = 0; k < NIT; ++k) {
+                    unsigned int t_, row, pp, o0;
+                    const bool ok = gelem(ln + 64u * k, t_, row, pp, o0);
+                    const unsigned int off = ok ? o0 + pp * (D * 8u) : 0u;
+                    v[k] = xt_gld(base, off);
+                    vn[k] = xt_gld(base, off + (ok && pp + 1 < (unsigned int)L ? D * 8u : 0u));
+                }
+                XT_UNROLL
+                for (int k = 0; k < NIT; ++k) {
+                    unsigned int t_, row, pp, o0;
+                    if (gelem(ln + 64u * k, t_, row, pp, o0)) cx.atomic_or_u32(&xt_at<uint32_t>(lds, gc0 + (int)t_ * 16 + (v[k] != v[k] ? 0 : 4)), 1u << row);
+                }
+                cx.wave_sync();
+                XT_UNROLL
+                for (int k = 0; k < NIT; ++k) {
+                    const unsigned int i = ln + 64u * k;
+                    unsigned int t_, row, pp, o0;
+                    if (!gelem(i, t_, row, pp, o0)) continue;
+                    const unsigned int gmm = xt_at<uint32_t>(lds, gc0 + (int)t_ * 16) & ~xt_at<uint32_t>(lds, gc0 + (int)t_ * 16 + 4);
+                    const bool isgap = (gmm >> row) & 1u;
+                    double cur = v[k];
+                    if (isgap) {
+                        const unsigned int x = ~gmm & (0xffffffffu >> (31u - row));  // observed rows of the chunk up to this one
+                        const unsigned int src = x ? (unsigned int)p0 + 31u - (unsigned int)__builtin_clz(x) : (unsigned int)xt_at<int>(lds, gc0 + (int)t_ * 16 + 8);
+                        cur = xt_gld(base, o0 + src * (D * 8u));
+                    }
+                    xt_at<double>(lds, xt_r2_pos0(0) + (wib * TPW * XT_F2_CHUNK * D + (int)i) * 8) = vn[k] != vn[k] ? 0.0 : vn[k] - cur;
+                    // a row with only some NaN coordinates, a missed first or last row: the track is NaN
+                    if ((v[k] != v[k] && !isgap) || (isgap && (pp == 0u || pp + 1u == (unsigned int)L))) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + (int)t_) * 4) = 1;
+                }
+                cx.wave_sync();
+                if (ln < (unsigned int)TPW) {
+                    const int cell = gc0 + (int)ln * 16;
+                    const int nrows = L - p0 < XT_F2_CHUNK ? L - p0 : XT_F2_CHUNK;
+                    const unsigned int valid = 0xffffffffu >> (32 - nrows);
+                    const unsigned int gmm = xt_at<uint32_t>(lds, cell) & ~xt_at<uint32_t>(lds, cell + 4) & valid, obs = ~gmm & valid;
+                    xt_at<uint32_t>(lds, cell) = gmm;  // what the steps read
+                    if (obs) xt_at<int>(lds, cell + 8) = p0 + 31 - __builtin_clz(obs);
+                    xt_at<int>(lds, cell + 12) += __builtin_popcount(gmm);
+                }
+                cx.wave_sync();
+                return;
+            }
             if constexpr (FAST) {
                 if (KS == 0 && (batch + 1) * TPW <= b.N) {
                     XT_UNROLL
@@ -835,6 +950,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 
         XtR2Lane<D, K, NP> s;
         double lam[2] = {0.0, 0.0};  // g-form launches: -2 x the log part of the members' weights (xt_r2_step_g); stays zero otherwise
+        unsigned int gmk = 0u;       // GAPS: the missed rows of this lane's track in the staged chunk (bit = row of the chunk)
 #define XT_R2_PHASE(H, ZF_, LAZY_)                                                                     \
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
@@ -847,7 +963,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
         getpos(t, c, l2);                                                                              \
-        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0)>(cx, lds, s, lam, pk, XT_R2_TABSEL, c);                   \
+        xt_r2_step_g<F, D, ((H) < NGB ? (H) : 0), false, GAPS>(cx, lds, s, lam, pk, XT_R2_TABSEL, c, GAPS && ((gmk >> (t & (XT_F2_CHUNK - 1))) & 1u)); \
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
@@ -908,12 +1024,19 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         int fe = XT_EMIN;
         int t = 1;
         if (lane < 8) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + lane) * 4) = 0;
+        if constexpr (GAPS) {
+            if (lane < 8) {
+                xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + lane) * 16 + 8) = 0;
+                xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + lane) * 16 + 12) = 0;
+            }
+        }
         if (NP == 0) {
             xt_at<int>(lds, rcacc()) = 0;
             xt_at<int>(lds, rcacc() - XT_R2_RC_ARR) = XT_R2_RC_NONE;  // the lane's own cell: the track's leader resets the one in use
         }
         for (int p0 = 0; p0 < L; p0 += XT_F2_CHUNK) {
             stage(p0);
+            if constexpr (GAPS) gmk = xt_at<uint32_t>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 16);
             if (p0 == 0) {
                 // ---- position 0: the initial state is the newest digit (group bit NGB - 1); dummy digits set -> zero weight
                 constexpr int NBIT = xt_r2_gbit(F, NGB - 1);
@@ -957,7 +1080,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                         bool chain_done = false;
                         if constexpr (K == 1) {
                             if (gform) {
-                                xt_r2_chain_g<F>(cx, lds, s, lam, T, stay_from, getpos);
+                                xt_r2_chain_g<F, D, GAPS>(cx, lds, s, lam, T, stay_from, getpos, gmk);
                                 s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lambda
                                 chain_done = true;
                             }
@@ -969,7 +1092,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                             bool first_done = false;
                             if constexpr (K == 1) {
                                 if (gform) {
-                                    xt_r2_step_g<F, D, NGB - 1, true>(cx, lds, s, lam, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c);
+                                    xt_r2_step_g<F, D, NGB - 1, true, GAPS>(cx, lds, s, lam, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, GAPS && ((gmk >> (F - 1)) & 1u));
                                     first_done = true;
                                 }
                             }
@@ -1125,7 +1248,9 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             const int lz = xt_opaque(cx.lane());
             const int64_t trk = batch * TPW + xt_r2_slot<F>(lz);  // formed again: not held across the step loop
             if (trk < b.N && (lz & GMASK) == 0) {
-                const double rcs = -0.5 * (double)xt_at<int>(lds, rcacc());  // the re-centring shifts, in lambda units; 0 unless log-carried steps ran
+                double rcs = -0.5 * (double)xt_at<int>(lds, rcacc());  // the re-centring shifts, in lambda units; 0 unless log-carried steps ran
+                // GAPS: + D/2 ln(2 pi l2) per missed row - its share of the bucket's ll_const and the D/2 ln l2 its steps left in lambda (xt_r2_step_g)
+                if constexpr (GAPS) rcs = xt_fma((double)xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(lz)) * 16 + 12), xt_at<double>(lds, XT_R2_GC_OFF), rcs);
                 if (b.ll_out) b.ll_out[trk] = log(sum) + (double)fe * XT_LN2 + b.ll_const + rcs;
                 xt_at<double>(lds, rcsum()) += rcs;
                 const int ab = accb();

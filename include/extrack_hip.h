@@ -175,7 +175,10 @@ int extrack_predict(extrack_ctx* ctx, const extrack_model* model, int32_t bucket
  * with only some NaN coordinates, makes the track's results NaN (as any NaN does in extrack_loglik).  The per-peak error of a gap row
  * is never read and may be NaN.  Posteriors: the state posterior of the gap position is returned like any other; the predictive
  * density of a position that was not observed does not weight the posterior of the state leaving the window at that step.
- * Served by gap-aware instantiations of the general fixed-window kernel (csrc/xt_kernel.h, two states included).  Decided on the
+ * Served by gap-aware instantiations of the general fixed-window kernel (csrc/xt_kernel.h); two-state likelihood launches (frame_len 5..7,
+ * and 4 in a context created under EXTRACK_GAP_REG2_F=all; one global scalar localisation error, a well-scaled model) by the gap-aware
+ * instantiation of the register-resident kernel (csrc/xt_reg2.h; EXTRACK_LL_PATH=lds keeps the general kernel; extrack_last_ll_path tells
+ * which ran).  Decided on the
  * host, nothing is launched, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2, n_states > 4, models whose sequence state does not fit a
  * workgroup (more than 1024 groups of sequences or more than 160 KiB of LDS per track), buckets with per-track time steps.
  * extrack_last_kernel_ms / extrack_last_launch_info cover the launches. */
@@ -410,6 +413,10 @@ int extrack_last_kernel_ms(extrack_ctx* ctx, float* ms);
 /* Launch geometry of the last track kernel: info[0] blocks, [1] threads/block, [2] LDS bytes/block,
  * [3] tracks/block, [4] occupancy (blocks/CU), [5] compute units. */
 int extrack_last_launch_info(const extrack_ctx* ctx, int32_t info[6]);
+/* Kernel family of the last launch group of extrack_loglik* / extrack_predict* / extrack_sequence_matrix (XtLlPath, csrc/xt_ll_geom.h):
+ * 1 register-resident 2-state, 2 LDS-resident 2-state, 3 entry-parallel, 4 general, 5 general with missed detections, 6 global-state,
+ * 7 register-resident 2-state with missed detections; 0 before any launch. */
+int extrack_last_ll_path(const extrack_ctx* ctx, int32_t* path);
 
 /* Host helper: p_stay table (extrack/tracking.py:182-191).  out has S^ns entries. */
 int extrack_p_stay_table(const double* ds, int32_t n_states, int32_t nb_substeps, const double* cell_dims,
