@@ -368,6 +368,10 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 #ifndef XT_R2_STAGE_FAST
 #define XT_R2_STAGE_FAST(D) ((D) < 3)
 #endif
+// lambda of a member that carries no sequence (y = 0: the dead member of a lane before the first full step, lanes whose digits are still dummies
+// at the end of a short bucket's chain): a quiet NaN (a constant the kernel already holds).  fmin passes it over, so it stays out of the
+// read-out's minimum; the exponential's clamp (x > c ? x : c) turns the NaN argument into c, and 0 x exp(c / 2) is the member's zero term.
+#define XT_R2_LAM_DEAD NAN
 #ifndef XT_R2_STAGE_GRP
 #define XT_R2_STAGE_GRP 4  // rounds of the wave whose loads are in flight together when a chunk is staged (xt_r2_body: stage)
 #endif
@@ -571,7 +575,8 @@ XT_HD void xt_r2_chain_g(Ctx& cx, char* lds, XtR2Lane<D, 1, 0>& s, double (&lam)
         if (i >= T) dummy |= 1 << xt_r2_gbit(F, i);
     const bool live = (lane & dummy) == 0;
     s.z[0] = live ? xt_frexp_mant(y) : 0.0;
-    lam[0] = xt_fma((double)xt_frexp_exp(y), -2.0 * XT_LN2, la);
+    const double lae = xt_fma((double)xt_frexp_exp(y), -2.0 * XT_LN2, la);
+    lam[0] = live ? lae : XT_R2_LAM_DEAD;  // only a bucket that goes from here straight to the read-out has such lanes
     s.u[0][0] = v;
 }
 
@@ -949,7 +954,12 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
 
         XtR2Lane<D, K, NP> s;
-        double lam[2] = {0.0, 0.0};  // g-form launches: -2 x the log part of the members' weights (xt_r2_step_g); stays zero otherwise
+        // g-form launches: -2 x the log part of the members' weights (xt_r2_step_g); member 1 is dead until the first full step gives it a value
+        // (which reads lam[0] alone).  Otherwise only read by the old read-out of a launch without g-form steps, where lam[1] meets z[1] = 0
+        double lam[2] = {0.0, 0.0};
+        if constexpr (NP == 0 && K == 1) {
+            if (gform) lam[1] = XT_R2_LAM_DEAD;
+        }
         unsigned int gmk = 0u;       // GAPS: the missed rows of this lane's track in the staged chunk (bit = row of the chunk)
 #define XT_R2_PHASE(H, ZF_, LAZY_)                                                                     \
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
@@ -1034,90 +1044,12 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             xt_at<int>(lds, rcacc()) = 0;
             xt_at<int>(lds, rcacc() - XT_R2_RC_ARR) = XT_R2_RC_NONE;  // the lane's own cell: the track's leader resets the one in use
         }
-        for (int p0 = 0; p0 < L; p0 += XT_F2_CHUNK) {
-            stage(p0);
-            if constexpr (GAPS) gmk = xt_at<uint32_t>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 16);
-            if (p0 == 0) {
-                // ---- position 0: the initial state is the newest digit (group bit NGB - 1); dummy digits set -> zero weight
-                constexpr int NBIT = xt_r2_gbit(F, NGB - 1);
-                double c0[D], l20[K];
-                getpos(0, c0, l20);
-                const bool live0 = chain || (lane & (GMASK & ~(1 << NBIT))) == 0;  // the chain masks the dummy digits at its end
-                const int s0 = (lane >> NBIT) & 1;
-                s.z[0] = live0 ? hdr[8 + s0] : 0.0;
-                s.e[0] = live0 ? 0 : XT_EMIN;
-                s.z[1] = 0.0;
-                s.e[1] = XT_EMIN;
-                XT_UNROLL
-                for (int q = 0; q < 2; ++q) {
-                    XT_UNROLL
-                    for (int d = 0; d < D; ++d) s.m[q][d] = c0[d];
-                    XT_UNROLL
-                    for (int k = 0; k < K; ++k) s.u[q][k] = l20[k];
-                }
-                if constexpr (NP == 0 && K == 1) {
-                    // g-form launches: the members carry r = c_next - m (position 0: the staged delta that getpos just read), v = l2 + u and
-                    // weights y exp(-lambda / 2), from here to the read-out of the last position
-                    if (gform) s.u[0][0] = s.u[1][0] = 2.0 * l20[0];
-                }
-                XT_UNROLL
-                for (int pp = 0; pp < NP; ++pp) {
-                    const int tb = XT_R2_TAN0 + pp * XT_R2_TB * 8;
-                    s.rz[pp][0] = live0 ? xt_at<double>(lds, tb + (8 + s0) * 8) : 0.0;
-                    s.rz[pp][1] = 0.0;
-                    XT_UNROLL
-                    for (int q = 0; q < 2; ++q) {
-                        XT_UNROLL
-                        for (int d = 0; d < D; ++d) s.dm[pp][q][d] = 0.0;
-                        XT_UNROLL
-                        for (int k = 0; k < K; ++k) s.du[pp][q][k] = xt_at<double>(lds, tb + k * 8);
-                    }
-                }
-                if constexpr (NP == 0) {
-                    if (chain) {
-                        // positions 1 .. F - 2 as per-lane chains, position F - 1 without the merge of the dead member: t = F after that
-                        const int T = L - 2 < NGB - 1 ? L - 2 : NGB - 1;
-                        bool chain_done = false;
-                        if constexpr (K == 1) {
-                            if (gform) {
-                                xt_r2_chain_g<F, D, GAPS>(cx, lds, s, lam, T, stay_from, getpos, gmk);
-                                s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lambda
-                                chain_done = true;
-                            }
-                        }
-                        if (!chain_done) xt_r2_chain<F>(cx, lds, s, T, stay_from, getpos);
-                        if (L - 2 >= F - 1) {
-                            double c[D], l2[K];
-                            getpos(F - 1, c, l2);
-                            bool first_done = false;
-                            if constexpr (K == 1) {
-                                if (gform) {
-                                    xt_r2_step_g<F, D, NGB - 1, true, GAPS>(cx, lds, s, lam, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, GAPS && ((gmk >> (F - 1)) & 1u));
-                                    first_done = true;
-                                }
-                            }
-                            if (!first_done) xt_r2_step<F, D, K, NP, NGB - 1, true, true, VAR, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, l2);
-                            t = F;
-                        } else {
-                            t = L - 1 > 1 ? L - 1 : 1;
-                        }
-                    }
-                }
-            }
-            const int tend = (L - 2 < p0 + XT_F2_CHUNK - 1) ? L - 2 : p0 + XT_F2_CHUNK - 1;
-            if (NP == 0) {
-                run_steps(t, tend < stay_from - 1 ? tend : stay_from - 1, XT_R2_TAB0);
-                run_steps(t, tend, XT_R2_TAB0 + 32);
-            } else {
-                run_steps_g(t, tend);
-            }
-            if (tlast < p0 || tlast >= p0 + XT_F2_CHUNK) continue;
-            // ---- last position (+ leaving / bleaching factor): reduction over (member Q, new digit q)
+        // ---- last position (+ leaving / bleaching factor): reduction over (member Q, new digit q), on the staged chunk that holds it (the last
+        // one).  The likelihood-only scalar-variance kernels run it after the chunk loop, so that none of its results is carried around that
+        // loop; g-form launches take the log-carried read-out there instead and never run this one.
+        auto readout = [&]() XT_INL {
             double cl[D], l2l[K];
             getpos(tlast, cl, l2l);
-            if constexpr (NP == 0 && K == 1) {
-                if (gform) l2l[0] = 0.0;  // g-form launches: the members carry v = l2 + u, and r = cl - m below
-            }
             const int hp = (tlast - 2 + NGB) % NGB;  // group bit of the newest digit
             const int pbit = (F == 7 || hp < 2) ? hp : hp + 1;
             const int prev = (lane >> pbit) & 1;
@@ -1143,9 +1075,6 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                 XT_UNROLL
                 for (int d = 0; d < D; ++d) {
                     dq[Q][d] = cl[d] - s.m[Q][d];
-                    if constexpr (NP == 0 && K == 1) {
-                        if (gform) dq[Q][d] = s.m[Q][d];
-                    }
                     dsqQ[Q] = xt_fma(dq[Q][d], dq[Q][d], dsqQ[Q]);
                 }
                 double x[2], gf[2];
@@ -1161,7 +1090,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                             rr[Q * 2 + q][0] = r;
                         }
                         if constexpr (NP == 0)
-                            x[q] = -0.5 * xt_fma(dsqQ[Q], r, lam[Q]);  // log-carried weights (xt_r2_step_g): y exp(-lambda / 2), e = 0; lambda = 0 otherwise
+                            x[q] = -0.5 * xt_fma(dsqQ[Q], r, lam[Q]);  // lambda = 0 here: launches with g-form steps never take this read-out
                         else
                             x[q] = -0.5 * dsqQ[Q] * r;
                         gf[q] = xt_pow_half<D>(r);
@@ -1239,16 +1168,168 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
                     uacc[u] = acc;
                 }
             }
+        };
+        for (int p0 = 0; p0 < L; p0 += XT_F2_CHUNK) {
+            stage(p0);
+            if constexpr (GAPS) gmk = xt_at<uint32_t>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 16);
+            if (p0 == 0) {
+                // ---- position 0: the initial state is the newest digit (group bit NGB - 1); dummy digits set -> zero weight
+                constexpr int NBIT = xt_r2_gbit(F, NGB - 1);
+                double c0[D], l20[K];
+                getpos(0, c0, l20);
+                const bool live0 = chain || (lane & (GMASK & ~(1 << NBIT))) == 0;  // the chain masks the dummy digits at its end
+                const int s0 = (lane >> NBIT) & 1;
+                s.z[0] = live0 ? hdr[8 + s0] : 0.0;
+                s.e[0] = live0 ? 0 : XT_EMIN;
+                s.z[1] = 0.0;
+                s.e[1] = XT_EMIN;
+                XT_UNROLL
+                for (int q = 0; q < 2; ++q) {
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) s.m[q][d] = c0[d];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) s.u[q][k] = l20[k];
+                }
+                if constexpr (NP == 0 && K == 1) {
+                    // g-form launches: the members carry r = c_next - m (position 0: the staged delta that getpos just read), v = l2 + u and
+                    // weights y exp(-lambda / 2), from here to the read-out of the last position
+                    if (gform) s.u[0][0] = s.u[1][0] = 2.0 * l20[0];
+                }
+                XT_UNROLL
+                for (int pp = 0; pp < NP; ++pp) {
+                    const int tb = XT_R2_TAN0 + pp * XT_R2_TB * 8;
+                    s.rz[pp][0] = live0 ? xt_at<double>(lds, tb + (8 + s0) * 8) : 0.0;
+                    s.rz[pp][1] = 0.0;
+                    XT_UNROLL
+                    for (int q = 0; q < 2; ++q) {
+                        XT_UNROLL
+                        for (int d = 0; d < D; ++d) s.dm[pp][q][d] = 0.0;
+                        XT_UNROLL
+                        for (int k = 0; k < K; ++k) s.du[pp][q][k] = xt_at<double>(lds, tb + k * 8);
+                    }
+                }
+                if constexpr (NP == 0) {
+                    if (chain) {
+                        // positions 1 .. F - 2 as per-lane chains, position F - 1 without the merge of the dead member: t = F after that
+                        const int T = L - 2 < NGB - 1 ? L - 2 : NGB - 1;
+                        bool chain_done = false;
+                        if constexpr (K == 1) {
+                            if (gform) {
+                                xt_r2_chain_g<F, D, GAPS>(cx, lds, s, lam, T, stay_from, getpos, gmk);
+                                s.e[0] = s.e[1] = 0;  // the read-out's integer exponents: all of the weight's scale is in lambda
+                                chain_done = true;
+                            }
+                        }
+                        if (!chain_done) xt_r2_chain<F>(cx, lds, s, T, stay_from, getpos);
+                        if (L - 2 >= F - 1) {
+                            double c[D], l2[K];
+                            getpos(F - 1, c, l2);
+                            bool first_done = false;
+                            if constexpr (K == 1) {
+                                if (gform) {
+                                    xt_r2_step_g<F, D, NGB - 1, true, GAPS>(cx, lds, s, lam, pk, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, GAPS && ((gmk >> (F - 1)) & 1u));
+                                    first_done = true;
+                                }
+                            }
+                            if (!first_done) xt_r2_step<F, D, K, NP, NGB - 1, true, true, VAR, true>(cx, lds, s, XT_R2_TAB0 + (F - 1 >= stay_from ? 32 : 0), c, l2);
+                            t = F;
+                        } else {
+                            t = L - 1 > 1 ? L - 1 : 1;
+                        }
+                    }
+                }
+            }
+            const int tend = (L - 2 < p0 + XT_F2_CHUNK - 1) ? L - 2 : p0 + XT_F2_CHUNK - 1;
+            if (NP == 0) {
+                run_steps(t, tend < stay_from - 1 ? tend : stay_from - 1, XT_R2_TAB0);
+                run_steps(t, tend, XT_R2_TAB0 + 32);
+            } else {
+                run_steps_g(t, tend);
+            }
+            if constexpr (!(NP == 0 && K == 1)) {
+                if (tlast >= p0 && tlast < p0 + XT_F2_CHUNK) readout();
+            }
         }
         // reduce over the track's lanes (every lane ends with the same values)
-        double sum = xt_r2_gsum<F>(cx, tot.m != 0.0 ? xt_ldexp(tot.m, tot.e - fe) : 0.0);
+        double lsum = 0.0;
+        int ronsh = 0;  // the shift of the log-carried read-out
+        bool ro_log = false;
+        if constexpr (NP == 0 && K == 1) {
+            if (gform) {
+                ro_log = true;
+                // ---- last position of a g-form launch, log-carried.  A member Q holds (y, lambda, r = c_last - m,
+                // v = l2 + u); its term for the new digit q is y Tfin rho^(D/2) exp(-a / 2), a = |r|^2 rho + lambda, rho = 1 / (d2 + v).
+                // ONE more re-centring instead of integer exponents: the track's smallest a (truncated and clamped as in xt_r2_step_g, through
+                // the same LDS cell) is taken out of every a, so the track's largest term has an argument in (-1/2, 1/2) and the terms add up
+                // as plain doubles (a negligible one underflows to 0); the shift goes back into the log-likelihood with the steps' shifts.
+                const int hpl = (tlast - 2 + NGB) % NGB;  // group bit of the newest digit
+                const int pbl = (F == 7 || hpl < 2) ? hpl : hpl + 1;
+                const int iol = ((xt_opaque(cx.lane()) >> pbl) & 1) * 16;  // [prev][0] byte offset
+                double d2l[2], tfl[2], dn[4], rho[4], aq[4], wq[4];  // wq: the terms' factors outside the exponential
+                XT_UNROLL
+                for (int q = 0; q < 2; ++q) {
+                    d2l[q] = xt_at<double>(lds, XT_R2_TAB0 + 4 * 32 + iol + q * 8);
+                    tfl[q] = xt_at<double>(lds, XT_R2_TAB0 + vfin * 32 + iol + q * 8);
+                }
+                XT_UNROLL
+                for (int i = 0; i < 4; ++i) dn[i] = d2l[i & 1] + s.u[i >> 1][0];
+                // the four rho from ONE reciprocal of the product of the dens (each in [1e-12, 1e4] on a well-scaled launch)
+                const double p01 = dn[0] * dn[1], p23 = dn[2] * dn[3];
+                const double R = xt_rcp3(p01 * p23);
+                const double r01 = R * p23, r23 = R * p01;
+                rho[0] = r01 * dn[1];
+                rho[1] = r01 * dn[0];
+                rho[2] = r23 * dn[3];
+                rho[3] = r23 * dn[2];
+                XT_UNROLL
+                for (int Q = 0; Q < 2; ++Q) {
+                    double rsq = 0.0;
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) rsq = xt_fma(s.m[Q][d], s.m[Q][d], rsq);
+                    aq[Q * 2] = xt_fma(rsq, rho[Q * 2], lam[Q]);
+                    aq[Q * 2 + 1] = xt_fma(rsq, rho[Q * 2 + 1], lam[Q]);
+                    wq[Q * 2] = (s.z[Q] * tfl[0]) * xt_pow_half<D>(rho[Q * 2]);
+                    wq[Q * 2 + 1] = (s.z[Q] * tfl[1]) * xt_pow_half<D>(rho[Q * 2 + 1]);
+                }
+                const double amin = fmin(fmin(aq[0], aq[1]), fmin(aq[2], aq[3]));  // dead members stay out (XT_R2_LAM_DEAD)
+                // the track's cell: a re-centring in the last step has left its shift there (reset one phase later); the next batch
+                // starts from its own reset
+                const int cell = xt_r2_rc0(D, 0, TPW) + (xt_r2_tid8(cx) & ~(GMASK * 8));
+                xt_at<int>(lds, cell) = XT_R2_RC_NONE;
+                cx.wave_sync();
+                cx.atomic_max_i32(&xt_at<int>(lds, cell), (int)fmin(fmax(-amin, -1e9), 1e9));  // NaN (poisoned track): a = +1e9
+                cx.wave_sync();
+                const int nsh = xt_at<int>(lds, cell);  // - min over the track's lanes
+                const double nsd = -(double)nsh;  // the argument below as a plain difference: the exponential's clamp stays the steps' constant
+                double acc = 0.0;
+                XT_UNROLL
+                for (int i = 0; i < 4; ++i) {
+                    double p;
+                    int j, n;
+                    xt_exp_tab_half_x1(nsd - aq[i], p, j, n);
+                    const double E = xt_ldexp(xt_at<double>(lds, XT_F2_EXPB_OFF + j * 8) * p, n);
+                    acc = xt_fma(wq[i], E, acc);
+                }
+                lsum = acc;
+                ronsh = nsh;
+                fe = 0;
+            }
+        }
+        if (!ro_log) {
+            if constexpr (NP == 0 && K == 1) readout();
+            lsum = tot.m != 0.0 ? xt_ldexp(tot.m, tot.e - fe) : 0.0;
+        }
+        double sum = xt_r2_gsum<F>(cx, lsum);
         const bool poisoned = xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + ts) * 4) != 0;
         if (poisoned) sum = NAN;  // NaN input -> NaN likelihood, as in the reference
         if (NP == 0) {
             const int lz = xt_opaque(cx.lane());
             const int64_t trk = batch * TPW + xt_r2_slot<F>(lz);  // formed again: not held across the step loop
             if (trk < b.N && (lz & GMASK) == 0) {
-                double rcs = -0.5 * (double)xt_at<int>(lds, rcacc());  // the re-centring shifts, in lambda units; 0 unless log-carried steps ran
+                // the re-centring shifts of the steps (the lane's cell) and of the log-carried read-out (added as doubles: up to 1e9 on a last-row
+                // outlier, which the 32-bit cell would not hold beside the steps' sum), in lambda units; 0 unless log-carried steps ran
+                const double rcs0 = 0.5 * ((double)ronsh - (double)xt_at<int>(lds, rcacc()));
+                double rcs = rcs0;
                 // GAPS: + D/2 ln(2 pi l2) per missed row - its share of the bucket's ll_const and the D/2 ln l2 its steps left in lambda (xt_r2_step_g)
                 if constexpr (GAPS) rcs = xt_fma((double)xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(lz)) * 16 + 12), xt_at<double>(lds, XT_R2_GC_OFF), rcs);
                 if (b.ll_out) b.ll_out[trk] = log(sum) + (double)fe * XT_LN2 + b.ll_const + rcs;

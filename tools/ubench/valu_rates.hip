@@ -42,6 +42,29 @@ __global__ void __launch_bounds__(256) k(double* out, double seed, int n, double
             if (OP == 18) x[c] = __builtin_fma(x[c], x[(c + 1) % CH], 0.5);    // inline constant
             if (OP == 19) y[c] = y[c] > i ? y[c] : x[c] > 1.0;                 // cmp/cndmask mix
             if (OP == 20) x[c] = __builtin_fma(x[c], x[(c + 1) % CH], x[(c + 2) % CH]);  // 3 VGPR-pair sources
+            // ---- the lane exchange and the selects of the 2-state step (xt_host.h: xor_i32 / pair_exchange_i32), and bare 64-bit instructions
+            if (OP == 21) y[c] = __builtin_amdgcn_update_dpp(y[c], y[c], 0xB1, 0xf, 0xf, false);   // v_mov_b32_dpp quad_perm:[1,0,3,2]
+            if (OP == 22) y[c] = __builtin_amdgcn_update_dpp(y[c], y[c], 0x128, 0xf, 0xf, false);  // v_mov_b32_dpp row_ror:8
+            if (OP == 23) {                                                                        // the bit-2 exchange: two moves under bank masks
+                const int r = __builtin_amdgcn_update_dpp(y[c], y[c], 0x104, 0xf, 0x5, false);
+                y[c] = __builtin_amdgcn_update_dpp(r, y[c], 0x114, 0xf, 0xA, false);
+            }
+            if (OP == 24 && (c & 1) == 0) {  // one swap serves two chains
+                const auto r = __builtin_amdgcn_permlane16_swap((unsigned)y[c], (unsigned)y[c + 1], false, false);
+                y[c] = (int)r[0], y[c + 1] = (int)r[1];
+            }
+            if (OP == 25 && (c & 1) == 0) {
+                const auto r = __builtin_amdgcn_permlane32_swap((unsigned)y[c], (unsigned)y[c + 1], false, false);
+                y[c] = (int)r[0], y[c + 1] = (int)r[1];
+            }
+            if (OP == 26) { asm volatile("v_cndmask_b32 %0, %0, %1, vcc" : "+v"(y[c]) : "v"(n)); }  // whatever vcc holds
+            if (OP == 32) { asm volatile("v_cmp_lt_u32 vcc, %0, %1\n\tv_cndmask_b32 %0, %0, %1, vcc" : "+v"(y[c]) : "v"(n) : "vcc"); }
+            if (OP == 33) { asm volatile("v_cmp_lt_u32 vcc, %0, %1" : : "v"(y[c]), "v"(n) : "vcc"); }
+            if (OP == 27) { asm volatile("v_bfe_u32 %0, %0, 1, 31" : "+v"(y[c])); }
+            if (OP == 28) { asm volatile("v_alignbit_b32 %0, %0, %1, 3" : "+v"(y[c]) : "v"(n)); }
+            if (OP == 29) { asm volatile("v_rcp_f64 %0, %0" : "+v"(x[c])); }
+            if (OP == 30) { asm volatile("v_ldexp_f64 %0, %0, 0" : "+v"(x[c])); }
+            if (OP == 31) { asm volatile("v_min_f64 %0, %0, %1" : "+v"(x[c]) : "v"(seed)); }
         }
     }
     double s = 0;
@@ -96,5 +119,20 @@ int main()
     run<18>("v_fma_f64 v, v, inline", d, 0);
     run<20>("v_fma_f64 v, v, v", d, 0);
     for (int rep = 0; rep < 3; ++rep) run<0>("v_fma_f64 (repeat, warm)", d, 0);
+    // lane exchange, selects and bare 64-bit instructions (profiles/readout_valu_rates.txt); the permlane rows: cycles per swap = 2 x the figure
+    run<21>("v_mov_b32_dpp quad_perm", d, 0);
+    run<22>("v_mov_b32_dpp row_ror:8", d, 0);
+    run<23>("bit-2 exch. (2 dpp + 1 mov)", d, 0);
+    run<24>("v_permlane16_swap_b32 / 2", d, 0);
+    run<25>("v_permlane32_swap_b32 / 2", d, 0);
+    run<26>("v_cndmask_b32", d, 0);
+    run<32>("v_cmp_lt_u32 + v_cndmask_b32", d, 1);
+    run<33>("v_cmp_lt_u32 alone", d, 0);
+    run<27>("v_bfe_u32", d, 0);
+    run<28>("v_alignbit_b32", d, 0);
+    run<29>("v_rcp_f64 (bare)", d, 0);
+    run<30>("v_ldexp_f64 (bare)", d, 0);
+    run<31>("v_min_f64", d, 0);
+    run<0>("v_fma_f64 (closing)", d, 0);
     return 0;
 }
