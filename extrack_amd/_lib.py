@@ -23,11 +23,14 @@ EXPORTS = [
     "extrack_multi_context", "extrack_multi_upload_bucket", "extrack_multi_clear_buckets", "extrack_multi_loglik",
     "extrack_loglik_gaps", "extrack_predict_gaps", "extrack_map_states_gaps", "extrack_refine_fixed_states_gaps",
     "extrack_loglik_grad_gaps", "extrack_loglik_grad_gaps_async", "extrack_loglik_scores_gaps", "extrack_loglik_scores_gaps_async",
-    "extrack_segment_len_hist_gaps", "extrack_last_ll_path",
+    "extrack_segment_len_hist_gaps", "extrack_last_ll_path", "extrack_last_grad_path",
 ]
 
 # XtLlPath (csrc/xt_ll_geom.h): the kernel family of a likelihood / posterior launch group, by code
 LL_PATH_NAMES = ("none", "reg2", "fast2", "entry", "general", "gaps", "big", "gaps_reg2")
+
+# XtGradPath (csrc/xt_grad_geom.h): the kernel family of a gradient / scores launch group, by code
+GRAD_PATH_NAMES = ("none", "rev", "reg2", "gradr", "lds", "gaps_reg2")
 
 _dp = C.POINTER(C.c_double)
 
@@ -115,6 +118,7 @@ def load():
     lib.extrack_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.extrack_last_launch_info.argtypes = [vp, C.POINTER(i32 * 6)]
     lib.extrack_last_ll_path.argtypes = [vp, C.POINTER(i32)]
+    lib.extrack_last_grad_path.argtypes = [vp, C.POINTER(i32)]
     lib.extrack_p_stay_table.argtypes = [vp, i32, i32, vp, i32, vp]
     lib.extrack_loglik_th.argtypes = [vp, C.POINTER(ExtrackModel), C.c_double, i32, i32, _dp, vp]
     lib.extrack_loglik_th_async.argtypes = [vp, C.POINTER(ExtrackModel), C.c_double, i32, i32, vp]
@@ -522,6 +526,13 @@ class Context:
         p = C.c_int32(0)
         self._check(self._lib.extrack_last_ll_path(self._h, C.byref(p)))
         return LL_PATH_NAMES[p.value]
+
+    def last_grad_path(self):
+        """Kernel family of the last gradient / scores launch group (extrack_last_grad_path): "rev", "reg2", "gradr", "lds", "gaps_reg2" (missed
+        detections on the register-resident 2-state kernels), or "none" before any launch."""
+        p = C.c_int32(0)
+        self._check(self._lib.extrack_last_grad_path(self._h, C.byref(p)))
+        return GRAD_PATH_NAMES[p.value]
 
 
 class MultiContext:

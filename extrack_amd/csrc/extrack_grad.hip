@@ -137,7 +137,7 @@ struct XtGradEval {
     std::vector<double> blob;  // the model blob on the host
     // the launch group in hand
     std::vector<XtBucketDesc> descs;
-    int D, K, KS, group_index = 0;
+    int D, K, KS, Lmax = 0, group_index = 0;  // Lmax: the longest track length of the group
     size_t doff, poff = 0;  // its descriptors in ctx->d_desc; the free rows of ctx->d_gpartials start here
     double* g_out;          // d_out for the first group; the later ones write a scratch row that group_done adds to d_out
 };
@@ -195,6 +195,8 @@ static int xt_grad_group_begin(XtGradEval& ev, const std::vector<XtBucket*>& g)
     const XtBucket& b0 = *g[0];
     ev.D = b0.D;
     ev.KS = b0.KS ? b0.KS : 1;
+    ev.Lmax = 0;
+    for (const XtBucket* b : g) ev.Lmax = std::max(ev.Lmax, (int)b->L);
     if (m->locerr_mode == 0) {
         ev.K = m->locerr_dims;
         if (ev.K != 1 && ev.K != ev.D) return xt_fail(ctx, EXTRACK_E_INVALID, "locerr_dims must be 1 or the track dimensionality");
@@ -339,9 +341,11 @@ static int xt_grad_rev_launch(XtGradEval& ev, const XtGradPick& pk)
     return EXTRACK_OK;
 }
 
-// two-state models: register-resident kernels (xt_reg2.h), <= 8 directions per pass, tangents in VGPRs
+// two-state models: register-resident kernels (xt_reg2.h), <= 8 directions per pass, tangents in VGPRs.  pk.path == XT_GRAD_GAPS_REG2 (a gapped
+// group upgraded by xt_grad_gap_reg2): the gap-aware instantiations and their block size; split, pass order and score columns are the same
 static int xt_grad_run_reg2(XtGradEval& ev, const XtGradPick& pk)
 {
+    const bool gap = pk.path == XT_GRAD_GAPS_REG2;
     extrack_ctx* ctx = ev.ctx;
     const extrack_model* m = ev.m;
     const int n_dir = ev.n_dir, TB = ev.TB;
@@ -372,10 +376,12 @@ static int xt_grad_run_reg2(XtGradEval& ev, const XtGradPick& pk)
     XtGradPass p = {};
     p.threads = pk.threads, p.tpb = pk.tpb, p.oversub = ctx->grad_knobs.oversub, p.r2 = true, p.NF = NF;
     p.well_scaled = xt_model_well_scaled(ev.blob, lo, hi) ? 1 : 0;
+    // gaps: the lazily normalised variant only under the gap-extended bound (xt_grad_gap_reg2_lazy), else the guarded one
+    if (gap) p.well_scaled = xt_grad_gap_reg2_lazy(p.well_scaled != 0, ev.Lmax, ev.blob.size() > 8 ? ev.blob[7] : NAN) ? 1 : 0;
     for (int p0 = 0; p0 < NF && !rc; p0 += per) {
         p.p0 = p0, p.NP = std::min(per, NF - p0), p.NU = p0 == 0 ? NUn : 0;
-        p.kp = xt_r2_kernel(ctx->cfg.F, ev.D, ev.K, p.NP);
-        p.lds = (size_t)xt_r2_block_bytes(p.NP + p.NU, ev.D, 0, pk.tpw);
+        p.kp = gap ? xt_r2_grad_gap_kernel(ctx->cfg.F, ev.D, p.NP) : xt_r2_kernel(ctx->cfg.F, ev.D, ev.K, p.NP);
+        p.lds = gap ? (size_t)xt_r2_grad_gap_block_bytes(p.NP + p.NU, ev.D, pk.tpw) : (size_t)xt_r2_block_bytes(p.NP + p.NU, ev.D, 0, pk.tpw);
         p.dblob = ctx->d_dblob2 + (size_t)p0 * TB;
         p.dst = xt_grad_dst_identity(0);  // column 1 + i of this launch -> the caller's direction index
         for (int i = 0; i < p.NP; ++i) p.dst.idx[i] = full[p0 + i];
@@ -449,11 +455,15 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
     XT_HIP(ctx, hipEventRecord(ctx->evg0, ctx->stream));
     for (const std::vector<XtBucket*>& g : groups) {
         if ((rc = xt_grad_group_begin(ev, g))) return rc;
-        const XtGradPick pk = xt_grad_pick(ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, g[0]->L, (int)g.size(), ctx->n_cu, gaps, d_scores != nullptr,
-                                           ctx->grad_knobs);
-        if (pk.path == XT_GRAD_NONE) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, xt_grad_refusal_text(pk.refusal));
-        rc = pk.path == XT_GRAD_REV ? xt_grad_rev_launch(ev, pk) : (pk.path == XT_GRAD_REG2 ? xt_grad_run_reg2(ev, pk) : xt_grad_run_passes(ev, pk));
+        const XtGradPick pk0 = xt_grad_pick(ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, g[0]->L, (int)g.size(), ctx->n_cu, gaps, d_scores != nullptr,
+                                            ctx->grad_knobs);
+        if (pk0.path == XT_GRAD_NONE) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, xt_grad_refusal_text(pk0.refusal));
+        // missed detections, two states: the gap-aware register-resident kernels where xt_grad_gap_reg2 says so (else pk0 as it is)
+        const XtGradPick pk = xt_grad_gap_reg2(pk0, ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, ev.Lmax, gaps, ctx->grad_knobs, ctx->gap_reg2_fmask);
+        rc = pk.path == XT_GRAD_REV ? xt_grad_rev_launch(ev, pk)
+                                    : (pk.path == XT_GRAD_REG2 || pk.path == XT_GRAD_GAPS_REG2 ? xt_grad_run_reg2(ev, pk) : xt_grad_run_passes(ev, pk));
         if (rc) return rc;
+        ctx->last_grad_path = pk.path;
         xt_grad_group_done(ev, g.size());
     }
     if (d_scores && d_opg) {
@@ -594,6 +604,13 @@ extern "C" int extrack_loglik_scores_gaps(extrack_ctx* ctx, const extrack_model*
                                           double* total_ll, double* grad, double* opg, double* scores)
 {
     return xt_loglik_scores_sync(ctx, m, n_dir, tangents, total_ll, grad, opg, scores, true);
+}
+
+extern "C" int extrack_last_grad_path(const extrack_ctx* ctx, int32_t* path)
+{
+    if (!ctx || !path) return EXTRACK_E_INVALID;
+    *path = ctx->last_grad_path;
+    return EXTRACK_OK;
 }
 
 extern "C" int extrack_last_grad_ms(extrack_ctx* ctx, float* ms)

@@ -29,3 +29,18 @@ const void* xt_r2_gap_kernel(int F, int D)
     if (F == 7) return xt_r2_gap_kernel_f7(D);
     return nullptr;
 }
+
+// The gap-aware gradient kernels (extrack_reg2_grad_gaps_f{4..7}.hip): kernel address for (frame_len, dims, directions per pass); one global
+// localisation error.  Built where xt_r2_gap_grad_built (xt_grad_geom.h) holds.
+const void* xt_r2_grad_gap_kernel_f4(int D, int NP);
+const void* xt_r2_grad_gap_kernel_f5(int D, int NP);
+const void* xt_r2_grad_gap_kernel_f6(int D, int NP);
+const void* xt_r2_grad_gap_kernel_f7(int D, int NP);
+const void* xt_r2_grad_gap_kernel(int F, int D, int NP)
+{
+    if (F == 4) return xt_r2_grad_gap_kernel_f4(D, NP);
+    if (F == 5) return xt_r2_grad_gap_kernel_f5(D, NP);
+    if (F == 6) return xt_r2_grad_gap_kernel_f6(D, NP);
+    if (F == 7) return xt_r2_grad_gap_kernel_f7(D, NP);
+    return nullptr;
+}

@@ -33,6 +33,8 @@ static inline bool xt_grad_dk_built(int D, int K) { return (K == 1 && D >= 1 && 
 static inline bool xt_rev_built(int G, int D, int K, int nbuf) { return G >= 2 && G <= 4 && (nbuf == 1 || nbuf == 2) && xt_grad_dk_built(D, K); }
 static inline bool xt_gradr_built(int G, int D, int K, int NPC) { return G >= 2 && G <= 4 && (NPC == 3 || NPC == 4) && xt_grad_dk_built(D, K); }
 static inline bool xt_r2_built(int F, int D, int K, int NP) { return F >= 4 && F <= 7 && NP >= 1 && NP <= 8 && xt_grad_dk_built(D, K); }
+// the gap-aware gradient kernels of xt_reg2.h (xt_r2_grad_gap_kernel, extrack_reg2.hip): one scalar localisation error
+static inline bool xt_r2_gap_grad_built(int F, int D, int K, int NP) { return F >= 4 && F <= 7 && NP >= 1 && NP <= 8 && K == 1 && D >= 1 && D <= 3; }
 // the LDS-resident kernel: any G without gaps (G outside 2 .. 4 runs the generic instantiation 0); both workgroup sizes
 static inline bool xt_grad_lds_built(int G, int D, int K, bool gaps) { return (!gaps || (G >= 2 && G <= 4)) && xt_grad_dk_built(D, K); }
 
@@ -90,7 +92,13 @@ static inline int xt_gradr_per_pass(int gradr_npc, int n_dir, int* NPC_out)
     return per;
 }
 
-enum XtGradPath { XT_GRAD_NONE = 0, XT_GRAD_REV, XT_GRAD_REG2, XT_GRAD_GRADR, XT_GRAD_LDS };
+enum XtGradPath { XT_GRAD_NONE = 0, XT_GRAD_REV, XT_GRAD_REG2, XT_GRAD_GRADR, XT_GRAD_LDS, XT_GRAD_GAPS_REG2 };
+// what extrack_last_grad_path reports as text (extrack_amd._lib.GRAD_PATH_NAMES is the same list)
+static inline const char* xt_grad_path_name(int p)
+{
+    static const char* const n[] = {"none", "rev", "reg2", "gradr", "lds", "gaps_reg2"};
+    return p >= 0 && p <= XT_GRAD_GAPS_REG2 ? n[p] : "none";
+}
 // why no kernel serves the group (all EXTRACK_E_UNSUPPORTED)
 enum XtGradRefusal { XT_GRAD_FITS = 0, XT_GRAD_NO_ONE_DIR, XT_GRAD_NO_GROUPS, XT_GRAD_NO_LDS, XT_GRAD_NO_VARIANT, XT_GRAD_NO_NP16 };
 static inline const char* xt_grad_refusal_text(int r)
@@ -183,5 +191,46 @@ static inline XtGradPick xt_grad_pick(const XtConfig& c, int D, int K, int locer
         if (p.refusal) return p;
     }
     p.path = XT_GRAD_LDS;
+    return p;
+}
+
+// ---- missed detections on the register-resident 2-state gradient kernels (xt_reg2.h: xt_r2_body<.., NP > 0, .., GAPS>)
+
+// Range of the LAZY variant of xt_r2_step (well_scaled != 0: mantissas re-normalised every XT_F2_RENORM = 3 phases) under gaps.
+// xt_model_well_scaled says: fractions and weights T, T * stay in [1e-20, 1], l2 + d2min >= 1e-12 and 2 l2 + d2max <= 1e4 - derived with
+// u <= l2, so that den = l2 + d2 + u is in [1e-12, 1e4].  A missed frame carries u' = u_bar + d2 forward instead of l2 tt <= l2, and a track
+// of the group has at most Lmax - 2 of them: u <= l2 + (Lmax - 2) d2max, den <= 1e4 + (Lmax - 2) d2max.  The lazy variant is launched only
+// when (Lmax - 2) d2max <= 1e4 as well: den in [1e-12, 2e4].  What the step needs then:
+//   * an observed step multiplies a mantissa by T den^(-D/2) e^x 2^(-n) with den^(-D/2) in [3.5e-7, 1e18] (1e-6 before) and the exponential's
+//     mantissa in [0.5, 1]; a missed step by T alone, in [1e-20, 1] - inside the observed step's interval.  Three un-normalised steps and two
+//     merges keep a mantissa within [1e-82, 4e54] ([1e-80, 1e55] before);
+//   * the shared reciprocal's argument Ws Dq0 Dq1 = W^3 den^2 is in [1e-270, 3e172]; rW = R d01 = 1 / Ws <= 1e82;
+//   * u'_q = U rW + d2_q = u_bar + d2_q <= 2e4 at a missed step, m'_q = M rW = m_bar; the read-out's den <= 2e4;
+//   * tangents are formed on normalised quantities (a_j = w_j / W, rq = 1 / den <= 1e12, tt in [0, 1)): a missed step adds d log T and dd2
+//     only.  ZF is off in both gradient variants, so a zero weight is handled as without gaps.
+// All far inside the fp64 range.  Beyond the bound the GUARDED variant runs (every mantissa normalised in every step, integer exponents:
+// nothing to bound); the upgrade is never refused for range.
+static inline bool xt_grad_gap_reg2_lazy(bool well_scaled, int Lmax, double d2max)
+{
+    return well_scaled && d2max == d2max && (double)(Lmax > 2 ? Lmax - 2 : 0) * d2max <= 1e4;
+}
+
+// The second decision of a gapped launch group, after xt_grad_pick (whose outputs do not change: a gapped two-state group still comes back as
+// XT_GRAD_GRADR): either `pk` unchanged or the geometry of the register-resident kernels as path XT_GRAD_GAPS_REG2.  Upgraded exactly when:
+// gaps and the pick is XT_GRAD_GRADR; S = 2, nb_substeps = 1, frame_len in fmask (extrack_ctx::gap_reg2_fmask: 5, 6, 7 by default, 4 under
+// EXTRACK_GAP_REG2_F=all - frame_len 4 of a default context keeps the geometry tests/test_hip_grad.py pins); kn.grad_reg2 == 1
+// (EXTRACK_GRAD_PATH=gradr | lds keep today's kernels); one global scalar error (locerr_mode 0, K = 1); n_dir > 0; the kernel is built.
+// Lmax is not part of the decision (the range only picks the variant, xt_grad_gap_reg2_lazy); it is an argument so that the launcher hands both
+// decisions the same group.
+static inline XtGradPick xt_grad_gap_reg2(const XtGradPick& pk, const XtConfig& c, int D, int K, int locerr_mode, int n_dir, int Lmax, bool gaps,
+                                          const XtGradKnobs& kn, int fmask)
+{
+    (void)Lmax;
+    if (!gaps || pk.path != XT_GRAD_GRADR) return pk;
+    if (c.F < 0 || c.F > 30 || !((fmask >> c.F) & 1) || !xt_use_reg2(c.S, c.NS, c.F)) return pk;
+    if (kn.grad_reg2 != 1 || locerr_mode != 0 || K != 1 || n_dir <= 0 || !xt_r2_gap_grad_built(c.F, D, K, 1)) return pk;
+    XtGradPick p;
+    p.path = XT_GRAD_GAPS_REG2;
+    p.tpw = 64 >> (c.F - 1), p.tpb = p.tpw * XT_F2_WAVES, p.threads = 64 * XT_F2_WAVES, p.maxnp = kn.r2_maxnp;
     return p;
 }

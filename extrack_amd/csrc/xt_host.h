@@ -316,6 +316,7 @@ struct extrack_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int32_t launch_info[6] = {0, 0, 0, 0, 0, 0};
+    int last_grad_path = 0;  // XtGradPath of the last gradient / scores launch group (extrack_last_grad_path), 0 before any
     int last_ll_path = 0;  // XtLlPath of the last likelihood / posterior / sequence-matrix launch group (extrack_last_ll_path), 0 before any
     std::map<std::pair<const void*, std::pair<int, size_t>>, int> occ_cache;
     int th_capE = 128;          // plan capacity (expanded sequences per step); grows on overflow
@@ -444,6 +445,7 @@ inline std::vector<std::vector<XtBucket*>> xt_launch_groups(extrack_ctx* ctx, si
 }
 __global__ void xt_reduce_partials(const double* __restrict__ partials, int n, double* __restrict__ out);
 const void* xt_r2_kernel(int F, int D, int K, int NP);  // extrack_reg2.hip: register-resident 2-state kernels, nullptr = not built
+const void* xt_r2_grad_gap_kernel(int F, int D, int NP);  // extrack_reg2.hip: gap-aware register-resident 2-state gradient kernels (one global error, NP 1..8), nullptr = not built
 const void* xt_r2_gap_kernel(int F, int D);  // extrack_reg2.hip: gap-aware register-resident 2-state likelihood kernels (one global error), nullptr = not built
 const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide);  // extrack_gaps.hip: gap-aware instantiations of xt_track_body (wide: more than 256 threads), nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers

@@ -1,7 +1,8 @@
 // Register-resident path of the track-likelihood recursion for TWO-STATE models with one substep (S = 2, ns = 1,
 // frame_len 4..7): log-likelihood (NP = 0) and log-likelihood + exact gradient along NP model directions (NP > 0).
-// GAPS (compile-time, default off: the instantiations without it are unchanged): the likelihood-only g-form path with missed detections
-// (all-NaN rows, DESIGN.md sections 18 and 25) - see xt_r2_step_g, xt_r2_chain_g and the staging in xt_r2_body.
+// GAPS (compile-time, default off: the instantiations without it are unchanged): missed detections (all-NaN rows) -
+// the likelihood-only g-form path (section 25: xt_r2_step_g, xt_r2_chain_g and the staging in xt_r2_body) and, for one scalar localisation
+// error, the gradient path (NP > 0, section 27: xt_r2_step<.., GAPS> and the staging of absolute positions in xt_r2_body).
 //
 // Reference: extrack/tracking.py:109-318 (P_Cs_inter_bound_stats), :76-98 (log_integrale_dif), :361-423 (fuse_tracks_general);
 // the gradient replaces the finite differences lmfit's BFGS takes around cum_Proba_Cs (tracking.py:1371).  Same mathematics as
@@ -69,6 +70,11 @@ XT_HD int xt_r2_block_bytes(int NP, int D, int KS, int tpw)
 // row before the chunk; int missed rows of the track so far}
 XT_HD int xt_r2_gap0(int D, int tpw) { return xt_r2_block_bytes(0, D, 0, tpw); }
 XT_HD int xt_r2_gap_block_bytes(int D, int tpw) { return xt_r2_gap0(D, tpw) + XT_F2_WAVES * 8 * 16; }
+// Gap-aware gradient launches (xt_r2_body<.., NP > 0, .., GAPS = true>), after everything xt_r2_block_bytes(NPT, D, 0, tpw)
+// counts (NPT = the pass's full + uniform directions): per (wave, slot) 16 bytes - {u32 rows of the staged chunk with a NaN coordinate, then:
+// rows that are missed frames; u32 rows with a finite coordinate; unused; int missed rows of the track so far}
+XT_HD int xt_r2_grad_gap0(int NPT, int D, int tpw) { return xt_r2_block_bytes(NPT, D, 0, tpw); }
+XT_HD int xt_r2_grad_gap_block_bytes(int NPT, int D, int tpw) { return xt_r2_grad_gap0(NPT, D, tpw) + XT_F2_WAVES * 8 * 16; }
 #define XT_R2_TAB0 (XT_BLOB_HDR * 8)  // byte address of table v = 0; table v at + v * 32, entry [prev][q] at + (prev * 2 + q) * 8
 // Derived constants of the g-form step (xt_r2_step_g), built per workgroup in the two gaps of the blob's 1 KiB that nothing else uses (the blob
 // ends at byte 800, the NaN flags take 832 .. 959): {-1 / (2 l2) (kept in the map; the ratio form of the step no longer reads it), 2 l2} and LT2[v][prev][q] = -2 lnT' = -2 (ln TAB[v][prev][q] - D/2 ln l2), v = 0 (T), 1 (T * stay)
@@ -96,10 +102,23 @@ struct XtR2Lane {
 // FIRST: step F - 1 right after the warm-up chain (xt_r2_chain; likelihood only, zero-free): member 1 is dead and member 0 holds a
 // normalised mantissa, so there is nothing to merge - the step runs on member 0 at unit weight scale (W = 1, M = m0, U = u0; Wm, We = z0, e0)
 // and its shared reciprocal covers Dq[0] Dq[1] only.
-template <int F, int D, int K, int NP, int H, bool ZF, bool LAZY, int VAR, bool FIRST = false, class Ctx>
-XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const double* c, const double* l2)
+// GAPS (gradient launches with one scalar localisation error; DESIGN.md sections 21, 27): `gap` = position t of this lane's track is a missed
+// frame.  The gap step is the observed step at the l2 -> infinity limit of its per-child factors: no Gaussian factor (z'_q = Wm TT[q] at exponent
+// We), gain tt_q -> 0 (m'_q = M rW), l2 tt_q -> d2_q + u_bar (u'_q = U rW + TD2[q]); tangents rz'_q = R + dlogT[q] (0 in a dead group),
+// dm'_q = dmb, du'_q = dd2_q + dub.  Per-lane SELECTS, no branch: the tracks of a wave (64 >> (F - 1) of them) miss different rows, and a branch
+// would cut the unrolled phase into basic blocks (see above what that cost once).  The selects sit where the fewest are needed - on the step's
+// SHARED factors rather than on every direction's results:
+//   * c - m_bar (dmW) := 0: the one place the position enters.  The staged position of a missed row is NaN; after this select nothing of the
+//     step depends on it (dn = 0, hd = 0, x = 0: a NaN and any number as the coordinate give the same bits);
+//   * tt_q := 0 and rq_q = 1 / den_q := 0 (hence Aq_q = 0, dtt_q = 0): with dn = 0 the tangent formulas below then give rz' = R + dlogT and
+//     dm' = dmb by themselves (fma(0, finite, x) = x: l2, dl are the model's ONE variance and the direction's constant, finite by validation);
+//   * the three results that the limit 0 * infinity hides are selected outright: z'_q (and its exponent increment n_q), u'_q, du'_q.
+// D + 8 double selects (and two integer ones) per step and 2 per direction, against 2 (2 + D) per step and as many per direction on the results.
+template <int F, int D, int K, int NP, int H, bool ZF, bool LAZY, int VAR, bool FIRST = false, bool GAPS = false, class Ctx>
+XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const double* c, const double* l2, bool gap = false)
 {
     static_assert(!FIRST || (NP == 0 && ZF && LAZY), "the merge-free first step is a step of the zero-free likelihood-only loop");
+    static_assert(!GAPS || (NP > 0 && K == 1 && !FIRST), "the gap-aware non-g-form step is the gradient step with one scalar localisation error");
     constexpr int NGB = F - 1;
     constexpr int XB = xt_r2_gbit(F, H), PB = xt_r2_gbit(F, (H + NGB - 1) % NGB);
     const int lane = xt_opaque(cx.lane());  // keeps the per-phase constants (prev, qa, table offsets) out of the loop-invariant registers
@@ -166,6 +185,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
     XT_UNROLL
     for (int d = 0; d < D; ++d) {
         dmW[d] = xt_fma(c[d], Ws, -M[d]);
+        if constexpr (GAPS) dmW[d] = gap ? 0.0 : dmW[d];
         if (K == 1) dsqW = xt_fma(dmW[d], dmW[d], dsqW);
     }
     double x[2], gf[2], tt[2][K];
@@ -175,6 +195,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
         if (K == 1) {
             x[q] = A * rD[q][0];
             tt[q][0] = xt_fma(Ws, TD2[q], U[0]) * rD[q][0];
+            if constexpr (GAPS) tt[q][0] = gap ? 0.0 : tt[q][0];
             gf[q] = xt_pow_half<D>(Ws * rD[q][0]);
         } else {
             double xx = 0.0, gg = 1.0;
@@ -198,6 +219,10 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
         int en = We + n[q];
         const double tj = xt_at<double>(lds, XT_F2_EXPB_OFF + j[q] * 8);
         double zn = (Wm * TT[q]) * (gf[q] * tj) * p[q];
+        if constexpr (GAPS) {
+            zn = gap ? Wm * TT[q] : zn;
+            en = gap ? We : en;
+        }
         if (!LAZY) {
             en += xt_frexp_exp(zn);
             zn = xt_frexp_mant(zn);
@@ -208,6 +233,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
         for (int d = 0; d < D; ++d) nm[q][d] = xt_fma(dmW[d], tt[q][K == 1 ? 0 : d], M[d]) * rW;
         XT_UNROLL
         for (int k = 0; k < K; ++k) nu[q][k] = l2[k] * tt[q][k];
+        if constexpr (GAPS) nu[q][0] = gap ? xt_fma(U[0], rW, TD2[q]) : nu[q][0];
     }
 
     // ---- tangents (formulas: header of xt_grad.h), all on normalised quantities; first the primal factors they share (kept few:
@@ -229,6 +255,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
             XT_UNROLL
             for (int k = 0; k < K; ++k) {
                 rq[q][k] = Ws * rD[q][k];  // 1 / den
+                if constexpr (GAPS) rq[q][k] = gap ? 0.0 : rq[q][k];
                 if (K == 1)
                     Aq[q][0] = -0.5 * rq[q][0] * xt_fma(-(dsqW * rW * rW), rq[q][0], (double)D);
                 else
@@ -292,6 +319,7 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
                     rzn = xt_fma(Aq[q][k], dden, rzn);
                     rzn = xt_fma(rq[q][k], hd[k], rzn);  // - r/2 * d|c - m_bar|^2
                     tdu[q][k] = xt_fma(l2[k], dtt[k], dl[k] * tt[q][k]);
+                    if constexpr (GAPS) tdu[q][k] = gap ? ds2 : tdu[q][k];
                 }
                 trz[q] = ZF ? rzn : (live ? rzn : 0.0);
                 XT_UNROLL
@@ -372,6 +400,11 @@ XT_HD void xt_r2_step(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int tab, const 
 // at the end of a short bucket's chain): a quiet NaN (a constant the kernel already holds).  fmin passes it over, so it stays out of the
 // read-out's minimum; the exponential's clamp (x > c ? x : c) turns the NaN argument into c, and 0 x exp(c / 2) is the member's zero term.
 #define XT_R2_LAM_DEAD NAN
+// What the staging of a gap-aware gradient launch leaves in LDS for an element it read as v: v itself (a missed row stays NaN).  tests/emul defines
+// it to put a finite number in place of a NaN, to show that no step uses the coordinates of a missed row.
+#ifndef XT_R2_GAP_STAGED
+#define XT_R2_GAP_STAGED(v) (v)
+#endif
 #ifndef XT_R2_STAGE_GRP
 #define XT_R2_STAGE_GRP 4  // rounds of the wave whose loads are in flight together when a chunk is staged (xt_r2_body: stage)
 #endif
@@ -674,12 +707,15 @@ XT_HD void xt_r2_chain(Ctx& cx, char* lds, XtR2Lane<D, K, NP>& s, int T, int sta
 }
 
 // NP == 0: log-likelihood only, per-block sums to a.partials (ga unused).  NP > 0: ga.gpartials[block][1 + NP] = {sum LL, sum dLL/dtheta_p}.
-// GAPS (likelihood only, K == 1, launches the host found fit for g-form steps: xt_ll_gap_reg2, xt_ll_geom.h): an all-NaN row is a missed frame
-// (DESIGN.md sections 18, 25); LDS of xt_r2_gap_block_bytes.
+// GAPS: an all-NaN row is a missed frame, K == 1.  NP == 0: launches the host found fit for g-form steps (xt_ll_gap_reg2,
+// xt_ll_geom.h; section 25), LDS of xt_r2_gap_block_bytes.  NP > 0: launches upgraded by xt_grad_gap_reg2 (xt_grad_geom.h; section 27), guarded
+// or lazily normalised steps as a.well_scaled says, LDS of xt_r2_grad_gap_block_bytes.
 template <int F, int D, int K, int NP, int VAR = 0, bool GAPS = false, class Ctx>
 XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
 {
-    static_assert(!GAPS || (NP == 0 && K == 1), "the gap-aware instantiation is the likelihood-only g-form path");
+    static_assert(!GAPS || K == 1, "the gap-aware instantiations have one scalar localisation error");
+    constexpr bool GG = GAPS && NP == 0;  // the likelihood-only g-form gap path
+    constexpr bool GN = GAPS && NP > 0;   // the gap-aware gradient path
     int lb, nb;
     const XtBucketDesc b = xt_bind_bucket(a, cx.block(), cx.nblocks(), lb, nb);
     typedef XtR2Geom<F> Gm;
@@ -708,7 +744,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     xt_f2_check_lds_base(lds);
     xt_f2_build_exp_table(cx, lds, XT_F2_EXPB_OFF, (const double*)(lds + XT_F2_T64_OFF));  // the 1024-entry table of xt_exp_tab_x2 from the blob's 64 entries
     // g-form steps (xt_r2_step_g): the launcher found one global localisation variance l2 >= 1e-12 in a well-scaled launch (well_scaled == 2)
-    const bool gform = GAPS || (NP == 0 && K == 1 && a.well_scaled == 2 && a.locerr_mode == 0);
+    const bool gform = GG || (NP == 0 && K == 1 && a.well_scaled == 2 && a.locerr_mode == 0);
     if constexpr (NP == 0 && K == 1) {
         if (gform && cx.tid() < 10) {
             const int i = cx.tid();
@@ -733,7 +769,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     // g-form steps: the [prev][q] table offsets of this lane's outputs in all F - 1 phases (xt_r2_pack_io), kept across the step loop instead of
     // the lane id
     int pk = xt_r2_pack_io<F, 0, Ctx>(lane);
-    const bool well_scaled = GAPS || a.well_scaled != 0;
+    const bool well_scaled = GG || a.well_scaled != 0;
     const bool chain = NP == 0 && well_scaled;  // warm-up as per-lane chains (xt_r2_chain)
 
     double* pos = (double*)(lds + xt_r2_pos0(NPT)) + wib * TPW * XT_F2_CHUNK * (D + KS);  // [TPW][CHUNK][D]
@@ -814,7 +850,46 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
         auto stage = [&](int p0) XT_INL {
             cx.wave_sync();  // the reads of the previous chunk are done
-            if constexpr (GAPS) {
+            if constexpr (GN) {
+                // Missed frames of a gradient launch: absolute positions are staged as they are (a missed row stays NaN: its step never uses
+                // it, xt_r2_step<.., GAPS>), so no stand-in row is needed - only the classification of section 25.  A row's coordinates may sit
+                // in different lanes, so every element ORs its row into the track's "has a NaN" or "has a finite" mask (LDS atomics); then one
+                // lane per slot forms missed = NaN & ~finite for the steps, counts the missed rows and poisons the track for a row with only
+                // some NaN coordinates or a missed first / last row.  Complete and partial batches alike (the empty slots of the last batch
+                // mirror the bucket's last track).
+                const int gc0 = xt_r2_grad_gap0(NPT, D, TPW) + wib * 8 * 16;
+                if (lane < 8) {
+                    xt_at<uint32_t>(lds, gc0 + lane * 16) = 0u;
+                    xt_at<uint32_t>(lds, gc0 + lane * 16 + 4) = 0u;
+                }
+                cx.wave_sync();
+                for (int i = lane; i < TPW * XT_F2_CHUNK * D; i += 64) {
+                    const int t_ = i / (XT_F2_CHUNK * D), r = i - t_ * (XT_F2_CHUNK * D);
+                    const int64_t tk = batch * TPW + t_;
+                    const int64_t tkc = tk < b.N ? tk : b.N - 1;
+                    if (p0 + r / D < L) {
+                        const double v = b.tracks[(tkc * L + p0) * D + r];
+                        pos[i] = XT_R2_GAP_STAGED(v);
+                        cx.atomic_or_u32(&xt_at<uint32_t>(lds, gc0 + t_ * 16 + (v != v ? 0 : 4)), 1u << (r / D));
+                    }
+                }
+                cx.wave_sync();
+                if (lane < TPW) {
+                    const int cell = gc0 + lane * 16;
+                    const int nrows = L - p0 < XT_F2_CHUNK ? L - p0 : XT_F2_CHUNK;
+                    const unsigned int valid = 0xffffffffu >> (32 - nrows);
+                    const unsigned int nanm = xt_at<uint32_t>(lds, cell) & valid, fin = xt_at<uint32_t>(lds, cell + 4) & valid;
+                    const unsigned int gmm = nanm & ~fin;
+                    // a row with only some NaN coordinates, a missed first or last row: the track is NaN
+                    if ((nanm & fin) || (p0 == 0 && (gmm & 1u)) || (L - p0 <= XT_F2_CHUNK && ((gmm >> (nrows - 1)) & 1u)))
+                        xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + lane) * 4) = 1;
+                    xt_at<uint32_t>(lds, cell) = gmm;  // what the steps read
+                    xt_at<int>(lds, cell + 12) += __builtin_popcount(gmm);
+                }
+                cx.wave_sync();
+                return;
+            }
+            if constexpr (GG) {
                 // Missed frames: a row is classified from ALL its coordinates (they may sit in different lanes, even rounds), so the chunk is
                 // staged in two passes around two row masks per track (LDS atomics).  Pass 1 loads every element and its successor and ORs the
                 // element's row into the NaN or the finite mask.  Pass 2 stages the deltas of the FILLED track: a missed row stands in as the last
@@ -965,7 +1040,7 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
     if (NGB > (H) && t <= tend2 && ph == (H)) {                                                        \
         double c[D], l2[K];                                                                            \
         getpos(t, c, l2);                                                                              \
-        xt_r2_step<F, D, K, NP, ((H) < NGB ? (H) : 0), ZF_, LAZY_, VAR>(cx, lds, s, XT_R2_TABSEL, c, l2);   \
+        xt_r2_step<F, D, K, NP, ((H) < NGB ? (H) : 0), ZF_, LAZY_, VAR, false, GN>(cx, lds, s, XT_R2_TABSEL, c, l2, GN && ((gmk >> (t & (XT_F2_CHUNK - 1))) & 1u)); \
         ++t;                                                                                           \
         ph = (H) + 1 == NGB ? 0 : (H) + 1;                                                             \
     }
@@ -1034,7 +1109,10 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         int fe = XT_EMIN;
         int t = 1;
         if (lane < 8) xt_at<int>(lds, XT_F2_NAN_OFF + (wib * 8 + lane) * 4) = 0;
-        if constexpr (GAPS) {
+        if constexpr (GN) {
+            if (lane < 8) xt_at<int>(lds, xt_r2_grad_gap0(NPT, D, TPW) + (wib * 8 + lane) * 16 + 12) = 0;
+        }
+        if constexpr (GG) {
             if (lane < 8) {
                 xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + lane) * 16 + 8) = 0;
                 xt_at<int>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + lane) * 16 + 12) = 0;
@@ -1171,7 +1249,8 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
         };
         for (int p0 = 0; p0 < L; p0 += XT_F2_CHUNK) {
             stage(p0);
-            if constexpr (GAPS) gmk = xt_at<uint32_t>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 16);
+            if constexpr (GG) gmk = xt_at<uint32_t>(lds, xt_r2_gap0(D, TPW) + (wib * 8 + xt_r2_slot<F>(xt_opaque(cx.lane()))) * 16);
+            if constexpr (GN) gmk = xt_at<uint32_t>(lds, xt_r2_grad_gap0(NPT, D, TPW) + (wib * 8 + ts) * 16);
             if (p0 == 0) {
                 // ---- position 0: the initial state is the newest digit (group bit NGB - 1); dummy digits set -> zero weight
                 constexpr int NBIT = xt_r2_gbit(F, NGB - 1);
@@ -1351,7 +1430,9 @@ XT_HD void xt_r2_body(const XtKernelArgs& a, const XtGradArgs& ga, Ctx& cx)
             XT_UNROLL
             for (int u = 0; u < XT_R2_MAXU; ++u) usum[u] = u < NU ? xt_r2_gsum<F>(cx, uacc[u]) : 0.0;
             if (act && leader) {
-                const double ll = log(sum) + (double)fe * XT_LN2 + b.ll_const;
+                double ll = log(sum) + (double)fe * XT_LN2 + b.ll_const;
+                // GAPS: + D/2 log 2 pi per missed row turns the bucket's ll_const (from L) into the track's (from its observed rows); model-independent
+                if constexpr (GN) ll = xt_fma((double)xt_at<int>(lds, xt_r2_grad_gap0(NPT, D, TPW) + (wib * 8 + ts) * 16 + 12), 0.5 * D * XT_LOG2PI, ll);
                 if (b.ll_out) b.ll_out[trk] = ll;
                 accp[0] += ll;
                 XT_UNROLL

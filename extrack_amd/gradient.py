@@ -180,7 +180,9 @@ def objective_and_gradient(params, ts, dt, cell_dims, nb_states, nb_substeps, fr
     ``comm``: extrack_amd.distributed.Comm - the (1 + nvar) vector is all-reduced over the ranks.
     ``threshold_fusion``: None = the fixed-window objective; (threshold, max_nb_states, chunk) = the threshold-fusion objective of
     extrack/tracking.py:427-743 and its gradient at the frozen plan of this evaluation (extrack_loglik_th_grad).
-    A ``TrackSet`` with ``.gaps`` (missed detections as all-NaN rows) goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps);
+    A ``TrackSet`` with ``.gaps`` (missed detections as all-NaN rows) goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps:
+    two states with one global localisation error at frame_len 5..7 run with the tangents in registers, xt_reg2.h; the rest
+    on xt_gradr.h / xt_grad.h, section 21; ``ts.ctx.last_grad_path()`` tells which);
     they are built for the fixed-window objective on one GPU: ``threshold_fusion`` or ``comm`` raise NotImplementedError."""
     from .tracking import _GAPS_NO_COMM, _GAPS_NO_THRESHOLD, _objective_model
     names = free_names(params) if names is None else list(names)

@@ -453,7 +453,8 @@ def cum_Proba_Cs_grad(params, names, all_tracks, dt, cell_dims, input_LocErr, nb
     minimises in v1.6.3): extrack_loglik_th_grad - the value is that of ``cum_Proba_Cs(..., fusion="threshold")`` and the gradient its
     derivative with the merge groups of THIS evaluation held fixed (the plan is re-decided at every call, exactly as the objective does).
     Same argument list as ``cum_Proba_Cs`` after ``names``; same prints; (+inf, zeros) for invalid parameters or NaN.
-    A ``TrackSet`` with ``gaps=True`` goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps; fusion="window", no ``comm``)."""
+    A ``TrackSet`` with ``gaps=True`` goes to the gap-aware forward-mode kernels (extrack_loglik_grad_gaps; fusion="window", no ``comm``): the
+    register-resident two-state kernels where they apply, else xt_gradr.h / xt_grad.h (section 21)."""
     from . import gradient
     th = _check_fusion(fusion)
     if th and comm is not None and not isinstance(all_tracks, TrackSet):

@@ -292,8 +292,10 @@ int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* model, in
  * + n_gaps * dims / 2 * log(2 pi) per track does not depend on the model and adds nothing to gradient and scores.  A NaN first or last
  * row, a row with only some NaN coordinates or a NaN error at an observed row gives the track a NaN LL and NaN scores.  Served by
  * gap-aware instantiations of the two forward-mode bodies (csrc/extrack_grad_gaps.hip): csrc/xt_gradr.h for up to 256 groups of
- * sequences per track, else csrc/xt_grad.h for up to 1024; the register-resident 2-state kernels and the reverse-mode kernels have no
- * gap-aware variant and are bypassed.  Decided on the host before anything is enqueued, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2,
+ * sequences per track, else csrc/xt_grad.h for up to 1024; two states with one global localisation error (locerr_mode 0, locerr_dims 1) at
+ * frame_len 5..7 (4 under EXTRACK_GAP_REG2_F) run on gap-aware instantiations of the register-resident kernels instead (csrc/xt_reg2.h,
+ * csrc/extrack_reg2_grad_gaps_f*.hip; EXTRACK_GRAD_PATH=gradr | lds keep the general ones; extrack_last_grad_path tells which ran); the
+ * reverse-mode kernels have no gap-aware variant and are bypassed.  Decided on the host before anything is enqueued, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2,
  * n_states > 4, buckets with per-track time steps, models that fit neither kernel.  n_dir == 0 is extrack_loglik_gaps (for the _async
  * form: evaluated synchronously, the sum then copied to d_out).  Scores: rows in bucket-upload order, ONE launch group, opg as in
  * extrack_loglik_scores.  Gap-free data gives the values of the plain calls up to the rounding of another kernel family (two states: the
@@ -417,6 +419,12 @@ int extrack_last_launch_info(const extrack_ctx* ctx, int32_t info[6]);
  * 1 register-resident 2-state, 2 LDS-resident 2-state, 3 entry-parallel, 4 general, 5 general with missed detections, 6 global-state,
  * 7 register-resident 2-state with missed detections; 0 before any launch. */
 int extrack_last_ll_path(const extrack_ctx* ctx, int32_t* path);
+/* Kernel family of the last launch group of extrack_loglik_grad* / extrack_loglik_scores* (XtGradPath, csrc/xt_grad_geom.h): 1 reverse mode,
+ * 2 register-resident 2-state, 3 registers + LDS exchange (xt_gradr.h), 4 LDS-resident (xt_grad.h), 5 register-resident 2-state with missed
+ * detections (a two-state _gaps launch with one global localisation error, frame_len 5..7, or 4 under EXTRACK_GAP_REG2_F;
+ * EXTRACK_GRAD_PATH=gradr | lds keep the general gap kernels); 0 before any launch.  A call without directions runs the likelihood kernels and
+ * leaves the value as it was. */
+int extrack_last_grad_path(const extrack_ctx* ctx, int32_t* path);
 
 /* Host helper: p_stay table (extrack/tracking.py:182-191).  out has S^ns entries. */
 int extrack_p_stay_table(const double* ds, int32_t n_states, int32_t nb_substeps, const double* cell_dims,
