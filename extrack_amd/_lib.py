@@ -30,7 +30,7 @@ EXPORTS = [
 LL_PATH_NAMES = ("none", "reg2", "fast2", "entry", "general", "gaps", "big", "gaps_reg2")
 
 # XtGradPath (csrc/xt_grad_geom.h): the kernel family of a gradient / scores launch group, by code
-GRAD_PATH_NAMES = ("none", "rev", "reg2", "gradr", "lds", "gaps_reg2")
+GRAD_PATH_NAMES = ("none", "rev", "reg2", "gradr", "lds", "gaps_reg2", "gaps_rev")
 
 _dp = C.POINTER(C.c_double)
 
@@ -529,7 +529,8 @@ class Context:
 
     def last_grad_path(self):
         """Kernel family of the last gradient / scores launch group (extrack_last_grad_path): "rev", "reg2", "gradr", "lds", "gaps_reg2" (missed
-        detections on the register-resident 2-state kernels), or "none" before any launch."""
+        detections on the register-resident 2-state kernels), "gaps_rev" (missed detections on the reverse-mode kernels), or "none" before any
+        launch."""
         p = C.c_int32(0)
         self._check(self._lib.extrack_last_grad_path(self._h, C.byref(p)))
         return GRAD_PATH_NAMES[p.value]

@@ -307,7 +307,8 @@ static int xt_grad_rev_launch(XtGradEval& ev, const XtGradPick& pk)
     extrack_ctx* ctx = ev.ctx;
     const XtConfig& c = ctx->cfg;
     const int TB = ev.TB, tpb = pk.tpb;
-    const void* kp = xt_rev_kernel_ptr(c.G, ev.D, ev.K, pk.nbuf);
+    // pk.path == XT_GRAD_GAPS_REV (a gapped group upgraded by xt_grad_gap_rev): the gap-aware instantiation of its twin, everything else as it is
+    const void* kp = pk.path == XT_GRAD_GAPS_REV ? xt_rev_gap_kernel_ptr(c.G, ev.D, ev.K, pk.nbuf) : xt_rev_kernel_ptr(c.G, ev.D, ev.K, pk.nbuf);
     if (!kp) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, "gradient kernel variant not built");
     if (pk.lds > 64 * 1024) XT_HIP(ctx, hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pk.lds));
     int occ = 0, rc;
@@ -459,8 +460,11 @@ static int xt_grad_enqueue(extrack_ctx* ctx, const extrack_model* m, int32_t n_d
                                             ctx->grad_knobs);
         if (pk0.path == XT_GRAD_NONE) return xt_fail(ctx, EXTRACK_E_UNSUPPORTED, xt_grad_refusal_text(pk0.refusal));
         // missed detections, two states: the gap-aware register-resident kernels where xt_grad_gap_reg2 says so (else pk0 as it is)
-        const XtGradPick pk = xt_grad_gap_reg2(pk0, ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, ev.Lmax, gaps, ctx->grad_knobs, ctx->gap_reg2_fmask);
-        rc = pk.path == XT_GRAD_REV ? xt_grad_rev_launch(ev, pk)
+        const XtGradPick pk1 = xt_grad_gap_reg2(pk0, ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, ev.Lmax, gaps, ctx->grad_knobs, ctx->gap_reg2_fmask);
+        // missed detections, any state count: reverse mode where the gap-free twin of the group would run it (never for a scores evaluation)
+        const XtGradPick pk = xt_grad_gap_rev(pk1, ctx->cfg, ev.D, ev.K, m->locerr_mode, n_dir, g[0]->L, (int)g.size(), ctx->n_cu, gaps, d_scores != nullptr,
+                                              ctx->grad_knobs);
+        rc = pk.path == XT_GRAD_REV || pk.path == XT_GRAD_GAPS_REV ? xt_grad_rev_launch(ev, pk)
                                     : (pk.path == XT_GRAD_REG2 || pk.path == XT_GRAD_GAPS_REG2 ? xt_grad_run_reg2(ev, pk) : xt_grad_run_passes(ev, pk));
         if (rc) return rc;
         ctx->last_grad_path = pk.path;

@@ -92,12 +92,12 @@ static inline int xt_gradr_per_pass(int gradr_npc, int n_dir, int* NPC_out)
     return per;
 }
 
-enum XtGradPath { XT_GRAD_NONE = 0, XT_GRAD_REV, XT_GRAD_REG2, XT_GRAD_GRADR, XT_GRAD_LDS, XT_GRAD_GAPS_REG2 };
+enum XtGradPath { XT_GRAD_NONE = 0, XT_GRAD_REV, XT_GRAD_REG2, XT_GRAD_GRADR, XT_GRAD_LDS, XT_GRAD_GAPS_REG2, XT_GRAD_GAPS_REV };
 // what extrack_last_grad_path reports as text (extrack_amd._lib.GRAD_PATH_NAMES is the same list)
 static inline const char* xt_grad_path_name(int p)
 {
-    static const char* const n[] = {"none", "rev", "reg2", "gradr", "lds", "gaps_reg2"};
-    return p >= 0 && p <= XT_GRAD_GAPS_REG2 ? n[p] : "none";
+    static const char* const n[] = {"none", "rev", "reg2", "gradr", "lds", "gaps_reg2", "gaps_rev"};
+    return p >= 0 && p <= XT_GRAD_GAPS_REV ? n[p] : "none";
 }
 // why no kernel serves the group (all EXTRACK_E_UNSUPPORTED)
 enum XtGradRefusal { XT_GRAD_FITS = 0, XT_GRAD_NO_ONE_DIR, XT_GRAD_NO_GROUPS, XT_GRAD_NO_LDS, XT_GRAD_NO_VARIANT, XT_GRAD_NO_NP16 };
@@ -233,4 +233,25 @@ static inline XtGradPick xt_grad_gap_reg2(const XtGradPick& pk, const XtConfig& 
     p.path = XT_GRAD_GAPS_REG2;
     p.tpw = 64 >> (c.F - 1), p.tpb = p.tpw * XT_F2_WAVES, p.threads = 64 * XT_F2_WAVES, p.maxnp = kn.r2_maxnp;
     return p;
+}
+
+// ---- missed detections on the reverse-mode kernels (xt_rev.h: xt_rev_body<.., GAPS = true>)
+
+// The third decision of a gapped launch group, applied to the result of xt_grad_gap_reg2 (xt_grad_pick's outputs do not change): gapped data go
+// where their gap-free twin would go.  Upgraded to XT_GRAD_GAPS_REV exactly when
+//   * gaps and not a per-track scores evaluation (reverse mode accumulates its adjoints across tracks);
+//   * pk.path is XT_GRAD_GRADR or XT_GRAD_LDS, or it is XT_GRAD_GAPS_REG2 and kn.grad_rev == 2 (EXTRACK_GRAD_PATH=rev: wherever built);
+//   * xt_grad_pick of the same group with gaps = false, scores = false returns XT_GRAD_REV: the kernel is built, the LDS fits, the log budget
+//     pays for max(n_cu / 2, nbuckets) blocks, and the knobs send the plain data to reverse mode (so EXTRACK_GRAD_PATH = gradr | lds | reg2
+//     keep the forward-mode kernels, and a two-state model with one global scalar error stays on gaps_reg2 / gradr).
+// The upgraded pick has that twin's geometry (tpb, threads, nbuf, lds, max_blocks, log_stride).  A refused group (XT_GRAD_NONE) stays refused.
+static inline XtGradPick xt_grad_gap_rev(const XtGradPick& pk, const XtConfig& c, int D, int K, int locerr_mode, int n_dir, int Lmax, int nbuckets,
+                                         int n_cu, bool gaps, bool scores, const XtGradKnobs& kn)
+{
+    if (!gaps || scores) return pk;
+    if (pk.path != XT_GRAD_GRADR && pk.path != XT_GRAD_LDS && !(pk.path == XT_GRAD_GAPS_REG2 && kn.grad_rev == 2)) return pk;
+    XtGradPick tw = xt_grad_pick(c, D, K, locerr_mode, n_dir, Lmax, nbuckets, n_cu, false, false, kn);
+    if (tw.path != XT_GRAD_REV) return pk;
+    tw.path = XT_GRAD_GAPS_REV;
+    return tw;
 }

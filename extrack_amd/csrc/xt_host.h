@@ -449,6 +449,7 @@ const void* xt_r2_grad_gap_kernel(int F, int D, int NP);  // extrack_reg2.hip: g
 const void* xt_r2_gap_kernel(int F, int D);  // extrack_reg2.hip: gap-aware register-resident 2-state likelihood kernels (one global error), nullptr = not built
 const void* xt_gap_kernel_ptr(int G, int D, int K, bool preds, bool wide);  // extrack_gaps.hip: gap-aware instantiations of xt_track_body (wide: more than 256 threads), nullptr = not built
 const void* xt_rev_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev.hip: reverse-mode gradient kernels (xt_rev.h), 1 | 2 exchange buffers
+const void* xt_rev_gap_kernel_ptr(int G, int D, int K, int nbuf);  // extrack_rev_gaps.hip: their gap-aware instantiations (xt_rev_body<.., GAPS = true>), nullptr = not built
 // threshold-fusion plan stage for other translation units (extrack_th.hip): `cb` gets, per launch group, the kernel arguments with the plan
 // made (a.buckets / a.chunk_end on the device), the track / error dimensionality, the largest group count of its chunks and the longest length
 typedef std::function<int(XtThArgs& a, int D, int K, int maxG, int Lmax)> XtThAfterPlan;

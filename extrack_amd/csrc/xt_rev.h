@@ -58,7 +58,13 @@ XT_HD size_t xt_rev_lds_bytes(int S, int G, int EP, int D, int K, int tpb, int t
 // the shift-register exchange needs whole sender groups: S^(F - NS) divisible by S^NS
 XT_HD bool xt_rev_supported(int G, int NG) { return G >= 2 && G <= 4 && NG >= G && NG % G == 0 && NG <= 256; }
 
-template <int G_, int D, int K, int NBUF, class Ctx>
+// GAPS (extrack_loglik_grad_gaps): a row whose coordinates are all NaN is a missed detection, staged and counted as in
+// xt_gradr_body<..., GAPS = true>.  Its forward step merges and logs as any step and expands by the transition alone,
+//     z'_q = W T_q,   m'_q = m_bar,   u'_q = d2_q + u_bar                                      (no l2, reciprocal, exponential, quadratic form)
+// and its adjoint is  M = sum_q mu'_q,  U = sum_q nu'_q,  lam_Q = a_Q (sum_q lam'_q + M . (m_Q - m_bar) + U . (u_Q - u_bar)),  mu_Q = a_Q M,
+// nu_Q = a_Q U,  log T[v][prev][q] += lam'_q,  d2[prev][q] += sum_k nu'_qk;  nothing goes to l2, slope or offset.  Positions 0 and L - 1 are
+// never gaps (such a track is poisoned).  Without the flag every `GAPS &&` below is a constant: the plain instantiations compile to the same code.
+template <int G_, int D, int K, int NBUF, bool GAPS = false, class Ctx>
 XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
 {
     int lb, nb;
@@ -84,6 +90,7 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
     double* X[2] = {tr0, tr0 + (NBUF - 1) * xdoubles};
     double* part = tr0 + NBUF * xdoubles;  // [XT_REV_PART]
     int* red_e = (int*)(part + XT_REV_PART);      // [0] exponent of the track total, [1] NaN-input flag
+    double* ngap = (double*)(red_e + 2);          // GAPS: missed detections of the track (the slot's last double, spare without the flag)
     double* spos = smem + reg0 + a.TPB * tdoubles + (tvalid ? slot : 0) * xt_stage_doubles(D);
     double* ssig = spos + XT_STAGE * D;
     auto XZ = [&](int r) XT_INL { return (int*)(X[r] + TC * EP); };
@@ -115,6 +122,10 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
     constexpr int A_T = 0, A_TF = 2 * G, A_D2 = 3 * G, A_L2 = 4 * G, A_SL = 4 * G + K, A_OF = 4 * G + K + 1, A_F = 4 * G + K + 2;
 
     if (tvalid && g == 0) red_e[1] = 0;
+    if (GAPS && tvalid && g == 0) {
+        *ngap = 0.0;
+        red_e[0] = XT_EMIN;  // GAPS resets the exponent behind a barrier (here and at the end of a batch), see the note at the plain reset below
+    }
     cx.sync();
 
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
@@ -124,6 +135,7 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
         const double* c = b.tracks + (act ? trk : 0) * (int64_t)L * D;
         const double* sg = b.sigma ? b.sigma + (act ? trk : 0) * (int64_t)L * a.KS : nullptr;
         int cur_blk = -1;
+        int cnt_blk = -1;  // GAPS: last block whose gaps are counted (the backward sweep stages the blocks again, in falling order)
 
         // positions [p0, p0 + XT_STAGE) of the track -> LDS (barrier before: nobody still reads the block being replaced)
         auto ensure = [&](int pos) XT_INL {
@@ -131,6 +143,35 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
             cur_blk = pos >> 5;
             const int p0 = cur_blk << 5;
             cx.sync();
+            if (GAPS) {
+                // row by row: all coordinates NaN = a gap (counted once; its error is copied but never looked at), some = a NaN input
+                const bool count = cur_blk > cnt_blk;
+                if (count) cnt_blk = cur_blk;
+                if (act) {
+                    double ng = 0.0;
+                    for (int r = g; r < XT_STAGE; r += NG)
+                        if (p0 + r < L) {
+                            int nn = 0;
+                            for (int d = 0; d < D; ++d) {
+                                const double v = c[(p0 + r) * D + d];
+                                spos[r * D + d] = v;
+                                nn += v != v ? 1 : 0;
+                            }
+                            const bool gap = nn == D;
+                            if ((nn != 0 && !gap) || (gap && (p0 + r == 0 || p0 + r == L - 1))) red_e[1] = 1;
+                            ng += gap ? 1.0 : 0.0;
+                            if (sg)
+                                for (int k = 0; k < a.KS; ++k) {
+                                    const double v = sg[(p0 + r) * a.KS + k];
+                                    ssig[r * a.KS + k] = v;
+                                    if (!gap && v != v) red_e[1] = 1;
+                                }
+                        }
+                    if (count && ng != 0.0) cx.atomic_add_f64(ngap, ng);
+                }
+                cx.sync();
+                return;
+            }
             if (act) {
                 for (int i = g; i < XT_STAGE * D; i += NG)
                     if (p0 + i / D < L) {
@@ -282,7 +323,11 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
             load_c(0, c0);
             load_l2(0, l20, sc0, sr0);
             init_members(c0, l20, zm, ze, mm, uu);
-            if (act && g == 0) red_e[0] = XT_EMIN;
+            // (plain: with L = 2 no barrier lies between this store and the atomic maximum of the last position, so a lane of another
+            // wavefront can in principle get there first and lose its exponent: the sum is then scaled by a smaller power of two, which
+            // changes the rounding of log(sw) and nothing else.  Seen on CPU threads only; kept as it is so that the plain kernels
+            // compile to the code they had)
+            if (!GAPS && act && g == 0) red_e[0] = XT_EMIN;
         }
 
         // =========================== forward sweep: positions 1 .. L-2, merged state of every step -> log
@@ -291,7 +336,8 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
             double ct[D], l2t[K], sct[K], srt[K], aj[G], mb[D], ub[K], Wm;
             int We;
             load_c(t, ct);
-            load_l2(t, l2t, sct, srt);
+            const bool gap = GAPS && ct[0] != ct[0];  // staged rows are all-NaN or poison the track: the first coordinate decides
+            if (!gap) load_l2(t, l2t, sct, srt);      // (the error of a gap row may be NaN: never read)
             merge(zm, ze, mm, uu, aj, mb, ub, Wm, We);
 #if defined(XT_REV_DIAG) && (XT_REV_DIAG & 2)
             if (act && t == 1) {
@@ -309,17 +355,29 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
             const double* TTl = t >= stay_from ? T1 : T0;
             double* xb = X[t & 1];
             int* xz = XZ(t & 1);
-            XT_UNROLL
-            for (int q = 0; q < G; ++q) {
-                double zo, mo[D], uo[K];
-                int eo;
-                expand(Wm, We, mb, ub, TTl[q], TD2[q], ct, l2t, zo, eo, mo, uo);
-                xb[widx[q]] = zo;
-                xz[widx[q]] = eo;
+            if (GAPS && gap) {  // transition-only step: a branch, not selects (lanes of another track may take the other side at the same t)
                 XT_UNROLL
-                for (int d = 0; d < D; ++d) xb[(1 + d) * EP + widx[q]] = mo[d];
+                for (int q = 0; q < G; ++q) {
+                    xb[widx[q]] = Wm * TTl[q];
+                    xz[widx[q]] = We > XT_EMIN ? We : XT_EMIN;
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) xb[(1 + d) * EP + widx[q]] = mb[d];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) xb[(1 + D + k) * EP + widx[q]] = TD2[q] + ub[k];
+                }
+            } else {
                 XT_UNROLL
-                for (int k = 0; k < K; ++k) xb[(1 + D + k) * EP + widx[q]] = uo[k];
+                for (int q = 0; q < G; ++q) {
+                    double zo, mo[D], uo[K];
+                    int eo;
+                    expand(Wm, We, mb, ub, TTl[q], TD2[q], ct, l2t, zo, eo, mo, uo);
+                    xb[widx[q]] = zo;
+                    xz[widx[q]] = eo;
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) xb[(1 + d) * EP + widx[q]] = mo[d];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) xb[(1 + D + k) * EP + widx[q]] = uo[k];
+                }
             }
             cx.sync();
             XT_UNROLL
@@ -401,7 +459,11 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
             for (int i = 0; i < XT_REV_PART && i < NG; ++i) sw += part[i];
             const bool poisoned = red_e[1] != 0;
             if (act && g == 0) {
-                const double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                double ll = poisoned ? NAN : log(sw) + (double)fe * XT_LN2 + b.ll_const;
+                if (GAPS) {  // b.ll_const counts every row of the bucket: give back the missed ones' share (no parameter in it)
+                    ll += *ngap * (0.5 * D * XT_LOG2PI);
+                    *ngap = 0.0;  // for the next batch (only this thread reads it, and no row is counted before the barrier that opens the next batch's staging)
+                }
                 if (b.ll_out) b.ll_out[trk] = ll;
                 ll_acc += ll;
             }
@@ -442,10 +504,12 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
 
         // =========================== backward sweep: positions L-2 .. 1
         double ctn[D], l2n[K], scn[K], srn[K];  // position t of the coming iteration
+        bool gapn = false;                      // GAPS: ... is a missed detection (position 0 never is)
         if (L >= 3) {
             ensure(L - 2);
             load_c(L - 2, ctn);
-            load_l2(L - 2, l2n, scn, srn);
+            gapn = GAPS && ctn[0] != ctn[0];
+            if (!gapn) load_l2(L - 2, l2n, scn, srn);
         }
         for (int t = L - 2; t >= 1; --t) {
             // the member adjoints (lam, mu, nu) of step t + 1 go back to the lanes that produced those members: adjoints of the outputs of step t
@@ -468,9 +532,11 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
                 sct[k] = scn[k];
                 srt[k] = srn[k];
             }
+            const bool gap = gapn;
             ensure(t - 1);
             load_c(t - 1, ctn);
-            load_l2(t - 1, l2n, scn, srn);
+            gapn = GAPS && t > 1 && ctn[0] != ctn[0];
+            if (!gapn) load_l2(t - 1, l2n, scn, srn);
             if (t == 1) {
                 init_members(ctn, l2n, zm, ze, mm, uu);
             } else {
@@ -490,17 +556,28 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
                     for (int d = 0; d < D; ++d) mbs[d] = lg[(1 + d) * NG + s];
                     XT_UNROLL
                     for (int k = 0; k < K; ++k) ubs[k] = lg[(1 + D + k) * NG + s];
-                    expand(Wms, Wes, mbs, ubs, TTs[sprev[Q] * G + q_s], TAB[(4 * S + sprev[Q]) * G + q_s], ctn, l2n, zm[Q], ze[Q], mm[Q], uu[Q]);
+                    if (GAPS && gapn) {  // position t - 1 was a missed detection: the gap rule, the operations of the forward sweep
+                        zm[Q] = Wms * TTs[sprev[Q] * G + q_s];
+                        ze[Q] = Wes > XT_EMIN ? Wes : XT_EMIN;
+                        XT_UNROLL
+                        for (int d = 0; d < D; ++d) mm[Q][d] = mbs[d];
+                        XT_UNROLL
+                        for (int k = 0; k < K; ++k) uu[Q][k] = TAB[(4 * S + sprev[Q]) * G + q_s] + ubs[k];
+                    } else {
+                        expand(Wms, Wes, mbs, ubs, TTs[sprev[Q] * G + q_s], TAB[(4 * S + sprev[Q]) * G + q_s], ctn, l2n, zm[Q], ze[Q], mm[Q], uu[Q]);
+                    }
                 }
             }
             double aj[G], mb[D], ub[K], Wm;
             int We;
             merge(zm, ze, mm, uu, aj, mb, ub, Wm, We);
             double dn[D], dsq = 0.0;
-            XT_UNROLL
-            for (int d = 0; d < D; ++d) {
-                dn[d] = ct[d] - mb[d];
-                dsq = xt_fma(dn[d], dn[d], dsq);
+            if (!(GAPS && gap)) {
+                XT_UNROLL
+                for (int d = 0; d < D; ++d) {
+                    dn[d] = ct[d] - mb[d];
+                    dsq = xt_fma(dn[d], dn[d], dsq);
+                }
             }
             cx.sync();
             // adjoints of the outputs of step t -> of its members, and of the tables on the way
@@ -516,45 +593,65 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
                 adn[d] = 0.0;
                 Ms[d] = 0.0;
             }
-            XT_UNROLL
-            for (int q = 0; q < G; ++q) {
-                const double lq = xb[widx[q]];
-                double mq[D], nq[K], r[K], tq[K], atq[K];
+            if (GAPS && gap) {  // adjoint of a transition-only step: no l2, slope, offset (a branch between the same barriers as the observed step)
                 XT_UNROLL
-                for (int d = 0; d < D; ++d) mq[d] = xb[(1 + d) * EP + widx[q]];
-                XT_UNROLL
-                for (int k = 0; k < K; ++k) nq[k] = xb[(1 + D + k) * EP + widx[q]];
-                const double d2 = TD2[q];
-                XT_UNROLL
-                for (int k = 0; k < K; ++k) {
-                    const double s2 = d2 + ub[k];
-                    r[k] = xt_rcp(l2t[k] + s2);
-                    tq[k] = s2 * r[k];
-                    atq[k] = nq[k] * l2t[k];
+                for (int q = 0; q < G; ++q) {
+                    const double lq = xb[widx[q]];
+                    double sd = 0.0;
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) Ms[d] += xb[(1 + d) * EP + widx[q]];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) {
+                        const double nq = xb[(1 + D + k) * EP + widx[q]];
+                        U[k] += nq;
+                        sd += nq;
+                    }
+                    Lam += lq;
+                    acc[A_T + q] += (act && !st) ? lq : 0.0;
+                    acc[A_T + G + q] += (act && st) ? lq : 0.0;
+                    acc[A_D2 + q] += act ? sd : 0.0;
                 }
+            } else {
                 XT_UNROLL
-                for (int d = 0; d < D; ++d) {
-                    const int kk = K == 1 ? 0 : d;
-                    atq[kk] = xt_fma(mq[d], dn[d], atq[kk]);
-                    adn[d] = xt_fma(mq[d], tq[kk], xt_fma(-lq * dn[d], r[kk], adn[d]));
-                    Ms[d] += mq[d];
+                for (int q = 0; q < G; ++q) {
+                    const double lq = xb[widx[q]];
+                    double mq[D], nq[K], r[K], tq[K], atq[K];
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) mq[d] = xb[(1 + d) * EP + widx[q]];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) nq[k] = xb[(1 + D + k) * EP + widx[q]];
+                    const double d2 = TD2[q];
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) {
+                        const double s2 = d2 + ub[k];
+                        r[k] = xt_rcp(l2t[k] + s2);
+                        tq[k] = s2 * r[k];
+                        atq[k] = nq[k] * l2t[k];
+                    }
+                    XT_UNROLL
+                    for (int d = 0; d < D; ++d) {
+                        const int kk = K == 1 ? 0 : d;
+                        atq[kk] = xt_fma(mq[d], dn[d], atq[kk]);
+                        adn[d] = xt_fma(mq[d], tq[kk], xt_fma(-lq * dn[d], r[kk], adn[d]));
+                        Ms[d] += mq[d];
+                    }
+                    double sd = 0.0;
+                    XT_UNROLL
+                    for (int k = 0; k < K; ++k) {
+                        const double A = K == 1 ? -0.5 * r[k] * xt_fma(-dsq, r[k], (double)D) : -0.5 * r[k] * xt_fma(-(dn[k] * dn[k]), r[k], 1.0);
+                        const double aden = xt_fma(lq, A, -atq[k] * tq[k] * r[k]);
+                        const double as2 = xt_fma(atq[k], r[k], aden);
+                        U[k] += as2;
+                        sd += as2;
+                        al2[k] += xt_fma(nq[k], tq[k], aden);
+                    }
+                    Lam += lq;
+                    acc[A_T + q] += (act && !st) ? lq : 0.0;
+                    acc[A_T + G + q] += (act && st) ? lq : 0.0;
+                    acc[A_D2 + q] += act ? sd : 0.0;
                 }
-                double sd = 0.0;
-                XT_UNROLL
-                for (int k = 0; k < K; ++k) {
-                    const double A = K == 1 ? -0.5 * r[k] * xt_fma(-dsq, r[k], (double)D) : -0.5 * r[k] * xt_fma(-(dn[k] * dn[k]), r[k], 1.0);
-                    const double aden = xt_fma(lq, A, -atq[k] * tq[k] * r[k]);
-                    const double as2 = xt_fma(atq[k], r[k], aden);
-                    U[k] += as2;
-                    sd += as2;
-                    al2[k] += xt_fma(nq[k], tq[k], aden);
-                }
-                Lam += lq;
-                acc[A_T + q] += (act && !st) ? lq : 0.0;
-                acc[A_T + G + q] += (act && st) ? lq : 0.0;
-                acc[A_D2 + q] += act ? sd : 0.0;
+                put_l2(al2, sct, srt);
             }
-            put_l2(al2, sct, srt);
             double M[D];
             XT_UNROLL
             for (int d = 0; d < D; ++d) M[d] = Ms[d] - adn[d];
@@ -601,6 +698,7 @@ XT_HD void xt_rev_body(const XtKernelArgs& a, const XtRevArgs& ra, Ctx& cx)
         }
         cx.sync();
         if (act && g == 0) red_e[1] = 0;
+        if (GAPS && tvalid && g == 0) red_e[0] = XT_EMIN;
     }
 
     // ---- block sums in a fixed order: every lane's accumulators -> LDS, one output column per thread

@@ -642,6 +642,11 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
     detections and the bucket keys are frame spans, as ``extrack_amd.gaps.insert_gaps`` makes them; the positions are integrated out
     exactly, DESIGN.md section 18.  Such fits difference the objective by default - ``gradient=None`` resolves to "fd" - and take the exact
     gradient of the gap-aware forward-mode kernels with ``gradient="forward"`` (a value that exists with ``gaps`` only).
+    Behind that entry point the launcher sends a gapped group where its gap-free twin would go: models with 3 or 4 states, and two-state models
+    with per-peak errors or frame_len 3, run the gap-aware reverse-mode kernels (one forward and one backward sweep whatever
+    the number of free parameters); two states with one scalar error stay on the register-resident kernels.
+    ``fit.gradient_kernel`` names the kernel family of the fit's last gradient evaluation - the text of ``Context.last_grad_path()``:
+    "gaps_rev", "gaps_reg2", "gradr", "lds", ...; "none" when the objective was differenced - and ``fit.gradient_why`` ends with it.
     They are built for fusion="window" on one GPU; ``gradient="analytic"`` and ``uncertainties`` stay refused with ``gaps`` - standard errors
     come from ``uncertainty.parameter_uncertainties(..., gaps=True)`` and ``uncertainty.attach``)."""
     from . import uncertainty
@@ -716,13 +721,19 @@ def param_fitting(all_tracks, dt, params=None, nb_states=2, nb_substeps=1, frame
                                                       fcn_grad=cum_Proba_Cs_grad)
         else:
             fit = minimize(cum_Proba_Cs, params, args=fargs, method=method, nan_policy="propagate")
+        # the kernel family of the fit's last gradient evaluation ("none": the optimiser differenced the objective); read before the
+        # uncertainties, whose scores calls launch kernels of their own
+        ctx = getattr(ts, "ctx", None)
+        ginfo["gradient_kernel"] = ctx.last_grad_path() if use_grad and fusion != "threshold" and hasattr(ctx, "last_grad_path") else "none"
+        if forward:
+            ginfo["gradient_why"] += "; the last evaluation ran %r" % ginfo["gradient_kernel"]
         if unc_method is not None:
             uncertainty.attach(fit, uncertainty.parameter_uncertainties(ts, dt, fit.params, nb_states, nb_substeps, frame_len, cell_dims, None,
                                                                         Matrix_type, device, unc_method, comm))
     finally:
         ts.close()
     # which way the optimiser got its gradient, and why (the fit's record; `ngev` > 0 says the same for the built-in driver)
-    fit.gradient_path, fit.gradient_why = ginfo["gradient_path"], ginfo["gradient_why"]
+    fit.gradient_path, fit.gradient_why, fit.gradient_kernel = ginfo["gradient_path"], ginfo["gradient_why"], ginfo["gradient_kernel"]
     if verbose == 0:
         print("")
     return fit

@@ -294,8 +294,11 @@ int extrack_loglik_scores_async(extrack_ctx* ctx, const extrack_model* model, in
  * gap-aware instantiations of the two forward-mode bodies (csrc/extrack_grad_gaps.hip): csrc/xt_gradr.h for up to 256 groups of
  * sequences per track, else csrc/xt_grad.h for up to 1024; two states with one global localisation error (locerr_mode 0, locerr_dims 1) at
  * frame_len 5..7 (4 under EXTRACK_GAP_REG2_F) run on gap-aware instantiations of the register-resident kernels instead (csrc/xt_reg2.h,
- * csrc/extrack_reg2_grad_gaps_f*.hip; EXTRACK_GRAD_PATH=gradr | lds keep the general ones; extrack_last_grad_path tells which ran); the
- * reverse-mode kernels have no gap-aware variant and are bypassed.  Decided on the host before anything is enqueued, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2,
+ * csrc/extrack_reg2_grad_gaps_f*.hip; EXTRACK_GRAD_PATH=gradr | lds keep the general ones; extrack_last_grad_path tells which ran).  A gradient
+ * call (not a scores call: reverse mode has no per-track scores) whose gap-free twin - the same group through extrack_loglik_grad - would run
+ * the reverse-mode kernels runs their gap-aware instantiations instead (csrc/xt_rev.h, csrc/extrack_rev_gaps.hip: 3 and 4 states; two states
+ * with per-peak errors or frame_len 3), one forward and one backward sweep whatever n_dir; EXTRACK_GRAD_PATH=gradr | lds |
+ * reg2, or a log budget (EXTRACK_REV_LOG_MB) too small for the group, keep the forward-mode kernels.  Decided on the host before anything is enqueued, EXTRACK_E_UNSUPPORTED: nb_substeps >= 2,
  * n_states > 4, buckets with per-track time steps, models that fit neither kernel.  n_dir == 0 is extrack_loglik_gaps (for the _async
  * form: evaluated synchronously, the sum then copied to d_out).  Scores: rows in bucket-upload order, ONE launch group, opg as in
  * extrack_loglik_scores.  Gap-free data gives the values of the plain calls up to the rounding of another kernel family (two states: the
@@ -422,7 +425,8 @@ int extrack_last_ll_path(const extrack_ctx* ctx, int32_t* path);
 /* Kernel family of the last launch group of extrack_loglik_grad* / extrack_loglik_scores* (XtGradPath, csrc/xt_grad_geom.h): 1 reverse mode,
  * 2 register-resident 2-state, 3 registers + LDS exchange (xt_gradr.h), 4 LDS-resident (xt_grad.h), 5 register-resident 2-state with missed
  * detections (a two-state _gaps launch with one global localisation error, frame_len 5..7, or 4 under EXTRACK_GAP_REG2_F;
- * EXTRACK_GRAD_PATH=gradr | lds keep the general gap kernels); 0 before any launch.  A call without directions runs the likelihood kernels and
+ * EXTRACK_GRAD_PATH=gradr | lds keep the general gap kernels), 6 reverse mode with missed detections (a _gaps gradient launch whose gap-free
+ * twin would run reverse mode); 0 before any launch.  A call without directions runs the likelihood kernels and
  * leaves the value as it was. */
 int extrack_last_grad_path(const extrack_ctx* ctx, int32_t* path);
 
