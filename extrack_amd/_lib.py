@@ -24,6 +24,7 @@ EXPORTS = [
     "extrack_loglik_gaps", "extrack_predict_gaps", "extrack_map_states_gaps", "extrack_refine_fixed_states_gaps",
     "extrack_loglik_grad_gaps", "extrack_loglik_grad_gaps_async", "extrack_loglik_scores_gaps", "extrack_loglik_scores_gaps_async",
     "extrack_segment_len_hist_gaps", "extrack_last_ll_path", "extrack_last_grad_path",
+    "extrack_predict_pairs", "extrack_predict_pairs_gaps",
 ]
 
 # XtLlPath (csrc/xt_ll_geom.h): the kernel family of a likelihood / posterior launch group, by code
@@ -113,6 +114,8 @@ def load():
     lib.extrack_predict.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
     lib.extrack_loglik_gaps.argtypes = [vp, C.POINTER(ExtrackModel), _dp, vp]
     lib.extrack_predict_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp]
+    lib.extrack_predict_pairs.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
+    lib.extrack_predict_pairs_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_map_states.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_map_states_gaps.argtypes = [vp, C.POINTER(ExtrackModel), i32, vp, vp]
     lib.extrack_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -485,6 +488,21 @@ class Context:
         out = np.empty((N, L, model.c.n_states))
         self._check((self._lib.extrack_predict_gaps if gaps else self._lib.extrack_predict)(self._h, C.byref(model.c), int(bucket_id), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def predict_pairs(self, model, bucket_id, pairs=True, counts=False, gaps=False):
+        """Pairwise state posteriors of one bucket (extrack_predict_pairs): ``pairs`` float64 [N, L-1, S, S], P(state t = i, state t+1 = j |
+        track), and / or ``counts`` float64 [N, S, S], their sum over t (with ``pairs=False`` only the counts cross the host).  Both asked:
+        the tuple (pairs, counts).  ``gaps``: all-NaN rows are missed detections (extrack_predict_pairs_gaps)."""
+        if not pairs and not counts:
+            raise ValueError("predict_pairs: ask for pairs, counts or both")
+        N, L, D, KS = self.buckets[bucket_id]
+        S = model.c.n_states
+        pr = np.empty((N, L - 1, S, S)) if pairs else None
+        ct = np.empty((N, S, S)) if counts else None
+        fn = self._lib.extrack_predict_pairs_gaps if gaps else self._lib.extrack_predict_pairs
+        self._check(fn(self._h, C.byref(model.c), int(bucket_id), pr.ctypes.data_as(C.c_void_p) if pairs else None,
+                       ct.ctypes.data_as(C.c_void_p) if counts else None))
+        return (pr, ct) if pairs and counts else (pr if pairs else ct)
 
     def map_states(self, model, bucket_id, scores=False, gaps=False):
         """Most-likely state path of every track of one bucket (extrack_map_states): int8 [N, L], and with ``scores`` the log joint

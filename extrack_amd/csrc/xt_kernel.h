@@ -46,6 +46,7 @@ struct XtBucketDesc {
     double ll_const;       // -(L-1)*D/2*log(2*pi)
     double* seq_out = nullptr;  // [N][E][G] log-weight of every (stored sequence, new digits) at the last position, or nullptr (xt_seqmat.h)
     double* scores_out = nullptr;  // forward-mode gradient kernels: row 0 of this bucket in the per-track score matrix [N][XtGradArgs::score_ld], or nullptr
+                                   // (PAIRS instantiations of xt_track_body: the per-track pair counts [N][S][S], or nullptr)
 };
 
 struct XtKernelArgs {
@@ -101,6 +102,8 @@ inline const double* xt_blob_ptr(const XtKernelArgs& a) { return a.blob ? a.blob
 XT_HD int xt_tab_doubles(int S, int G) { return XT_BLOB_HDR + XT_NTAB * S * G + 64; }  // + T64[j] = 2^(j/64)
 XT_HD int xt_region_doubles(int E, int D, int K) { return E * (1 + D + K) + (E + 1) / 2 + 2; }
 XT_HD int xt_pred_doubles(int S, int F) { return 2 * (S + 1) + (F + 1) * S + 2; }
+// PAIRS instantiations: pe[2] (ints, in one double) + spare, pacc[2][S][S], facc[F][S][S], cacc[S][S] (the track's running counts)
+XT_HD int xt_pair_doubles(int S, int F) { return 2 + (F + 3) * S * S; }
 #define XT_STAGE 32  // positions of a track staged in LDS per refill (coalesced loads instead of a dependent global load per step)
 XT_HD int xt_stage_doubles(int D) { return XT_STAGE * (D + XT_MAX_DIMS); }
 // Storage index of logical sequence i.  For power-of-two S consecutive groups are 2^k / 4^k sequences apart, an up to
@@ -148,7 +151,12 @@ XT_HD XtBucketDesc xt_bind_bucket(const XtKernelArgs& a, int block, int nblocks,
 // usual, but no Gaussian factor; the mean stays the fused mean and the stored u becomes d2 + ub (the l2 -> infinity limit of l2*s2/(l2+s2)).
 // The row's per-peak error is never read.  The first and the last row must be observed and a row with only some NaN coordinates is no gap: both
 // poison the track as any NaN does without GAPS.  The per-track constant counts the observed rows: -(n_observed - 1) * D/2 * log(2 pi).
-template <int G_, int D, int K, bool PREDS, bool GAPS = false, class Ctx>
+//
+// PAIRS (compile-time, default off, with PREDS): instead of the posterior of the digit that leaves the window, the joint
+// posterior of that digit and the next one - from the same weights, kept apart by the oldest digit of the group (g % S: xt_build_config fills
+// base_tab oldest digit first) instead of summed over it.  preds_out is then [N][L-1][S][S] (or nullptr) and scores_out the per-track sum
+// over the positions [N][S][S] (or nullptr); the launch always goes through bucket descriptors.
+template <int G_, int D, int K, bool PREDS, bool GAPS = false, bool PAIRS = false, class Ctx>
 XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
 {
     int lb, nb;
@@ -176,12 +184,16 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
     int* ze = (int*)(uu + K * EP);
     int* red_e = ze + ((EP + 1) & ~1);  // [2] ints: final-reduce exponent, spare
     double* ngap = (double*)(red_e + 2);  // GAPS: missed detections of the track, counted where its rows are staged (the region's last double)
-    double* pbase = smem + ((ntab + 1) & ~1) + a.TPB * rdoubles + (tvalid ? slot : 0) * xt_pred_doubles(S, F);
-    // PREDS accumulators: pe[2] (ints, in one double), pacc[2][S], facc[F+1][S]
+    static_assert(!PAIRS || (PREDS && G_ >= 2), "PAIRS: a posterior instantiation with a compile-time group size");
+    const int SS = S * S;  // PAIRS: (state, next state) entries of one position
+    const int pdoubles = PAIRS ? xt_pair_doubles(S, F) : xt_pred_doubles(S, F);
+    double* pbase = smem + ((ntab + 1) & ~1) + a.TPB * rdoubles + (tvalid ? slot : 0) * pdoubles;
+    // PREDS accumulators: pe[2] (ints, in one double), pacc[2][S], facc[F+1][S]     (PAIRS: pacc[2][S][S], facc[F][S][S], cacc[S][S])
     int* pe = (int*)pbase;
     double* pacc = pbase + 2;
-    double* facc = pacc + 2 * S;
-    double* spos = smem + ((ntab + 1) & ~1) + a.TPB * (rdoubles + xt_pred_doubles(S, F)) + (tvalid ? slot : 0) * xt_stage_doubles(D);
+    double* facc = pacc + 2 * (PAIRS ? SS : S);
+    double* cacc = facc + F * SS;  // PAIRS only
+    double* spos = smem + ((ntab + 1) & ~1) + a.TPB * (rdoubles + pdoubles) + (tvalid ? slot : 0) * xt_stage_doubles(D);
     double* ssig = spos + XT_STAGE * D;
 
     const int prev = g / a.prev_div;
@@ -204,6 +216,30 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
             case 8: return cx.template group_sum_f64<8>(v);
             case 4: return cx.template group_sum_f64<4>(v);
             default: return cx.template group_sum_f64<2>(v);
+        }
+    };
+    // PAIRS: one sum per oldest digit of the group (g % S) instead of one per track.  The lanes of a range that share g % S are those that agree
+    // in the lowest log2(S) bits: the butterfly leaves those strides out, and lanes 0 .. S-1 of the range end up with the S sums.
+    const int gs = g % S;
+    auto res_sum = [&](double v) -> double {
+        if (G_ == 2 && gl > 2) v += cx.template xor_f64<1>(v);
+        if (gl > 4) v += cx.template xor_f64<2>(v);
+        if (gl > 8) v += cx.template xor_f64<3>(v);
+        if (gl > 16) v += cx.template xor_f64<4>(v);
+        if (gl > 32) v += cx.template xor_f64<5>(v);
+        return v;
+    };
+    // ... and one per newest digit of the group (g / prev_div): contiguous lanes, the all-reduce over min(range, prev_div) of them
+    const int gw = a.prev_div < gl ? a.prev_div : gl;
+    auto new_sum = [&](double v) -> double {
+        switch (gw) {
+            case 64: return cx.template group_sum_f64<64>(v);
+            case 32: return cx.template group_sum_f64<32>(v);
+            case 16: return cx.template group_sum_f64<16>(v);
+            case 8: return cx.template group_sum_f64<8>(v);
+            case 4: return cx.template group_sum_f64<4>(v);
+            case 2: return cx.template group_sum_f64<2>(v);
+            default: return v;
         }
     };
     const int64_t nbatch = (b.N + a.TPB - 1) / a.TPB;
@@ -304,7 +340,7 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
                 red_e[0] = XT_EMIN;
                 if (PREDS) {
                     pe[0] = pe[1] = XT_EMIN;
-                    for (int i = 0; i < 2 * S + (F + 1) * S; ++i) pacc[i] = 0.0;
+                    for (int i = 0; i < (PAIRS ? (F + 3) * SS : 2 * S + (F + 1) * S); ++i) pacc[i] = 0.0;
                 }
             }
         }
@@ -447,6 +483,35 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
             cx.sync();
             if (PREDS && do_pred) {
                 const int pem = act ? pe[par] : 0;
+                if (PAIRS) {
+                    // pq[Q] of this thread belongs to the pair (Q, g % S)
+                    if (lane_sums) {
+                        for (int Q = 0; Q < G; ++Q) {
+                            const double sQ = res_sum((act && pq[Q].m != 0.0) ? xt_ldexp(pq[Q].m, pq[Q].e - pem) : 0.0);
+                            if (act && (g & (gl - 1)) < S && sQ != 0.0) cx.atomic_add_f64(&pacc[par * SS + Q * S + gs], sQ);
+                        }
+                    } else if (act) {
+                        for (int Q = 0; Q < G; ++Q)
+                            if (pq[Q].m != 0.0) cx.atomic_add_f64(&pacc[par * SS + Q * S + gs], xt_ldexp(pq[Q].m, pq[Q].e - pem));
+                    }
+                    if (act) {
+                        for (int i = g; i < SS; i += NG) pacc[(par ^ 1) * SS + i] = 0.0;
+                        if (g == 0) pe[par ^ 1] = XT_EMIN;
+                    }
+                    cx.sync();
+                    if (act && g < SS) {
+                        double tot = 0.0;
+                        for (int s = 0; s < SS; ++s) tot += pacc[par * SS + s];
+                        // S^2 values per step, S^(F-1) threads per track: at frame_len 2 every thread writes S of them.  Entry i is always
+                        // this thread's, so its running count needs no atomic and is summed in the order of t
+                        for (int i = g; i < SS; i += NG) {
+                            const double v = pacc[par * SS + i] / tot;
+                            if (b.preds_out) b.preds_out[(trk * (L - 1) + (t - F)) * SS + i] = v;
+                            cacc[i] += v;
+                        }
+                    }
+                    continue;
+                }
                 if (lane_sums) {
                     for (int Q = 0; Q < G; ++Q) {
                         const double sQ = lane_sum((act && pq[Q].m != 0.0) ? xt_ldexp(pq[Q].m, pq[Q].e - pem) : 0.0);
@@ -538,7 +603,23 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
         cx.sync();  // all reads of the state are done: zm can be reused as reduction scratch
         int fe = XT_EMIN;
         if (act) fe = red_e[0];
-        if (lane_sums) {
+        if (PAIRS) {
+            // pair column c = the states of the positions L-2-c and L-1-c.  Column 0: (newest digit of g, q) from accq; column F-1: (Q, g % S)
+            // from accQ; the F-2 columns between: two neighbouring digits of g, from the thread's total (below)
+            if (lane_sums) {
+                for (int q = 0; q < G; ++q) {
+                    const double s0 = new_sum((act && accq[q].m != 0.0) ? xt_ldexp(accq[q].m, accq[q].e - fe) : 0.0);
+                    const double sF = res_sum((act && L - 1 >= F && accQ[q].m != 0.0) ? xt_ldexp(accQ[q].m, accQ[q].e - fe) : 0.0);
+                    if (act && (g & (gw - 1)) == 0 && s0 != 0.0) cx.atomic_add_f64(&facc[prev * S + q], s0);
+                    if (act && (g & (gl - 1)) < S && sF != 0.0) cx.atomic_add_f64(&facc[(F - 1) * SS + q * S + gs], sF);
+                }
+            } else if (act) {
+                for (int q = 0; q < G; ++q) {
+                    if (accq[q].m != 0.0) cx.atomic_add_f64(&facc[prev * S + q], xt_ldexp(accq[q].m, accq[q].e - fe));
+                    if (L - 1 >= F && accQ[q].m != 0.0) cx.atomic_add_f64(&facc[(F - 1) * SS + q * S + gs], xt_ldexp(accQ[q].m, accQ[q].e - fe));
+                }
+            }
+        } else if (lane_sums) {
             // column 0 = newest digit q; column F = fused slot digit Q: the same S addresses for every thread of the track
             for (int q = 0; q < G; ++q) {
                 const double s0 = lane_sum((act && accq[q].m != 0.0) ? xt_ldexp(accq[q].m, accq[q].e - fe) : 0.0);
@@ -551,7 +632,14 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
         }
         if (act) {
             zm[g] = tot.m != 0.0 ? xt_ldexp(tot.m, tot.e - fe) : 0.0;
-            if (PREDS) {
+            if (PAIRS) {
+                const double al = zm[g];
+                if (al != 0.0)
+                    for (int c = 1; c <= F - 2 && c <= L - 2; ++c) {
+                        const int two = (g / a.pw[F - c - 2]) % SS;  // digit c+1 of g (the older one) in the low place, digit c above it
+                        cx.atomic_add_f64(&facc[c * SS + (two % S) * S + two / S], al);
+                    }
+            } else if (PREDS) {
                 const double al = zm[g];
                 // columns 1..F-1 = digits of g
                 if (!lane_sums)
@@ -579,7 +667,23 @@ XT_HD void xt_track_body(const XtKernelArgs& a, Ctx& cx)
             if (b.ll_out) b.ll_out[trk] = ll;
             block_ll += ll;
         }
-        if (PREDS && act) {
+        if (PAIRS && act) {
+            // in the order of t (column ncol-1 first), entry i by the thread that owned it in the loop
+            const int ncol = L - 1 < F ? L - 1 : F;
+            for (int c = ncol - 1; c >= 0 && g < SS; --c) {
+                double tots = 0.0;
+                for (int s = 0; s < SS; ++s) tots += facc[c * SS + s];
+                for (int i = g; i < SS; i += NG) {
+                    const double v = facc[c * SS + i] / tots;
+                    if (b.preds_out) b.preds_out[(trk * (L - 1) + (L - 2 - c)) * SS + i] = v;
+                    cacc[i] += v;
+                }
+            }
+            if (b.scores_out)
+                for (int i = g; i < SS; i += NG) b.scores_out[trk * SS + i] = poisoned ? NAN : cacc[i];
+            if (poisoned && b.preds_out)
+                for (int i = g; i < (L - 1) * SS; i += NG) b.preds_out[trk * (L - 1) * SS + i] = NAN;
+        } else if (PREDS && act) {
             const int ncol = (L - 1 < F ? L - 1 : F) + 1;
             for (int i = g; i < ncol * S; i += NG) {
                 const int j = i / S;

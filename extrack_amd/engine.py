@@ -240,6 +240,11 @@ class TrackSet:
             return [self.ctx.predict(model, i, gaps=True) for i in range(len(self.shapes))]
         return [self.ctx.predict(model, i) for i in range(len(self.shapes))]
 
+    def predict_pairs(self, model, pairs=True, counts=False):
+        """Pairwise state posteriors for every uploaded bucket, in upload order: list of float64 arrays [N_l, l-1, S, S] (``pairs``), of
+        [N_l, S, S] (``counts``, their sum over the positions; with ``pairs=False`` nothing else crosses the host), or of tuples of both."""
+        return [self.ctx.predict_pairs(model, i, pairs=pairs, counts=counts, gaps=self.gaps) for i in range(len(self.shapes))]
+
     def map_states(self, model, scores=False):
         """Most-likely state path for every uploaded bucket, in upload order: list of int8 arrays [N_l, l]; with ``scores`` a list of
         (states, float64 [N_l] log joint density of track and path)."""

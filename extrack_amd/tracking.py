@@ -841,3 +841,74 @@ def predict_states(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len
         finally:
             ts.close()
     return (states, scores) if return_scores else states
+
+
+_PAIR_OUTPUTS = ("pairs", "counts", "both")
+
+
+def predict_transitions(all_tracks, dt, params, cell_dims=[1], nb_states=2, frame_len=6, input_LocErr=None, device=None, gaps=False,
+                        output="pairs", fusion="window", comm=None):
+    """Posterior of every pair of consecutive states, P(state at position t = i, state at position t+1 = j | track): where a track switches
+    state and how sure the model is of it (the reference has nothing of the kind; ``predict_states`` gives one hard path).  DESIGN.md
+    section 29.
+
+    ``output="pairs"``: {str(len): float64 ndarray[n_tracks, len-1, nb_states, nb_states]}; ``"counts"``: {str(len): float64
+    ndarray[n_tracks, nb_states, nb_states]}, the sum over the positions = the expected number of i -> j transitions of each track (only
+    these cross the host then); ``"both"``: the tuple (pairs, counts).  Keyed by every input key (correctly shaped empty arrays for empty
+    buckets), rows in input order.  ``nb_substeps`` is 1 and min / max length come from all keys, as in ``predict_Bs``.
+
+    The pairs are taken from exactly the weights ``predict_Bs(fusion="window")`` takes the posterior of position t from, so their sum over
+    j is that posterior at every t.  Their sum over i is the posterior of position t+1 only inside the last window (t >= len - 1 -
+    frame_len): before it the two are read at different lags of the fixed-lag approximation.  Tracks of at most frame_len + 1 positions get
+    the exact pair posterior.  A track with a NaN position or error is NaN everywhere.
+
+    ``gaps``: all-NaN rows are missed detections (``extrack_amd.gaps.insert_gaps``); the rules of ``TrackSet(gaps=True)`` are checked on the
+    host (ValueError naming bucket and track, before any device call) and pairs that involve a missed frame are returned like any other.
+    ``transition_matrix`` turns the counts into the data set's soft transition-count matrix and its row-normalised form."""
+    if output not in _PAIR_OUTPUTS:
+        raise ValueError("output must be 'pairs', 'counts' or 'both'")
+    if not is_parameters(params):
+        raise TypeError("params must be either of the class 'lmfit.parameter.Parameters' or a dictionary of the relevant parameters")
+    if _check_fusion(fusion):
+        raise NotImplementedError(_GAPS_NO_THRESHOLD if gaps else "predict_transitions reads the fixed-window recursion only: use fusion='window'")
+    if isinstance(dt, dict):
+        raise NotImplementedError("predict_transitions is not built for per-track time steps (dt as a dict of arrays)")
+    if comm is not None:
+        raise NotImplementedError(_GAPS_NO_COMM if gaps else "predict_transitions is not built for distributed evaluation: run it on one GPU (comm=None)")
+    keys, tracks, sigmas = engine.sort_buckets(all_tracks, input_LocErr)
+    le, Ds, Fs, TrMat, pBL, so = _extract_arrays(params, dt, 1, 1)
+    ds = np.sqrt(2 * Ds * dt)
+    S = len(ds)
+    want_pairs, want_counts = output != "counts", output != "pairs"
+    pairs = {l: np.empty((0, max(int(l) - 1, 0), S, S)) for l in keys}
+    counts = {l: np.empty((0, S, S)) for l in keys}
+    if tracks:
+        ts = TrackSet(tracks, sigmas, device=_resolve_device(device, None), min_len=max(int(keys[0]), 2), max_len=int(keys[-1]), gaps=gaps)
+        try:
+            if sigmas is not None:
+                model = ts.make_model(None, ds, Fs, TrMat, pBL, cell_dims, 1, frame_len, slope_offset=so)
+            else:
+                model = ts.make_model(le[None, None], ds, Fs, TrMat, pBL, cell_dims, 1, frame_len)
+            for arr, res in zip(tracks, ts.predict_pairs(model, pairs=want_pairs, counts=want_counts)):
+                pr, ct = res if output == "both" else ((res, None) if want_pairs else (None, res))
+                if want_pairs:
+                    pairs[str(arr.shape[1])] = pr
+                if want_counts:
+                    counts[str(arr.shape[1])] = ct
+        finally:
+            ts.close()
+    return (pairs, counts) if output == "both" else (pairs if want_pairs else counts)
+
+
+def transition_matrix(counts):
+    """The data set's soft transition-count matrix and its row-normalised form from the per-track counts of
+    ``predict_transitions(..., output="counts")``: ``counts`` a dict {str(len): [n_tracks, S, S]} (or one such array).  Returns (C [S, S],
+    the expected number of i -> j steps summed over all tracks, NaN tracks left out; P [S, S] = C / C.sum(axis=1): the one-step EM
+    re-estimate of the per-step transition matrix, to be held against the fitted one; a state that is never occupied gives a NaN row)."""
+    arrs = [np.asarray(v, float) for v in (counts.values() if isinstance(counts, dict) else [counts])]
+    arrs = [a for a in arrs if a.size]
+    if not arrs:
+        raise ValueError("transition_matrix: no counts")
+    tot = sum(a[np.isfinite(a).all(axis=(1, 2))].sum(axis=0) for a in arrs)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return tot, tot / tot.sum(axis=1, keepdims=True)

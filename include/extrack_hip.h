@@ -207,6 +207,28 @@ int extrack_map_states(extrack_ctx* ctx, const extrack_model* model, int32_t buc
  * EXTRACK_E_UNSUPPORTED here (as in extrack_loglik_gaps); gap-free data gives the same bits. */
 int extrack_map_states_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, int8_t* states, double* score);
 
+/* Pairwise state posteriors of one bucket (nothing of the kind in the reference): pairs host [n][len-1][n_states][n_states] or NULL,
+ * pairs[k][t][i][j] = P(state of position t = i, state of position t+1 = j | track k); counts host [n][n_states][n_states] or NULL,
+ * counts[k][i][j] = sum over t of pairs[k][t][i][j], the expected number of i -> j transitions of the track (summed in the order of t).
+ * With pairs NULL only the counts leave the device.  nb_substeps is 1.
+ * Definition: the pair is taken from exactly the weights from which extrack_predict takes the posterior of position t.  A position that
+ * leaves the window (t <= len - 2 - frame_len) is read when it is the oldest digit of the window, weighted by the predictive density of the
+ * next position as the reference weights it (extrack/tracking.py:255-271, its missing 1/2 on the log term included): the pair is the oldest
+ * and the second-oldest digit.  The remaining positions come from the final sequence weights, as neighbouring digits.  So
+ *     sum over j of pairs[k][t][i][j] = preds[k][t][i] of extrack_predict for EVERY t (to rounding), while
+ *     sum over i of pairs[k][t][i][j] = preds[k][t+1][j] holds only for t >= len - 1 - frame_len (inside the last window); before that the
+ * two sides are read at different lags of the fixed-lag approximation.  For len <= frame_len + 1 nothing is fused and the pairs are exact.
+ * extrack_predict_pairs_gaps: all-NaN rows are missed detections with the weights of extrack_predict_gaps (at a gap step the transition
+ * factor alone weights the leaving digit); pairs that involve a missed frame are returned like any other.  A track that extrack_predict
+ * (extrack_predict_gaps) makes NaN is NaN everywhere, counts included.
+ * Served by the PAIRS instantiations of the fixed-window kernel (csrc/xt_kernel.h), two states included; extrack_last_ll_path reports
+ * "general" or "gaps".  Both outputs NULL: EXTRACK_E_INVALID.  Decided on the host, nothing is launched: nb_substeps != 1 (refused as
+ * extrack_predict / extrack_predict_gaps refuse it), and EXTRACK_E_UNSUPPORTED for n_states > 4, for n_states^(frame_len - 1) > 1024 or a
+ * sequence state with pair accumulators beyond the 160 KiB LDS of a CU, and for buckets with per-track time steps.
+ * extrack_last_kernel_ms / extrack_last_launch_info cover the launch. */
+int extrack_predict_pairs(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double* pairs, double* counts);
+int extrack_predict_pairs_gaps(extrack_ctx* ctx, const extrack_model* model, int32_t bucket_id, double* pairs, double* counts);
+
 /* Tangent of a model along one direction theta: d(field)/d(theta) for every differentiable field of extrack_model.
  * The diffusion lengths enter as the derivative of their SQUARES (ds^2 = 2 D dt is what the recursion uses, and it keeps the
  * derivative finite at D = 0).  p_stay is a function of ds and cell_dims computed by the caller (extrack_p_stay_table), so its
